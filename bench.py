@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- Mvoxels/s of the voxel graph cut (build + solve) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C] [--strong] [--no-cpu] [--no-extras] [--cpu-full]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C] [--strong] [--dump-outputs DIR]
+                    [--full [--no-cpu] [--no-extras] [--cpu-full]]
 
 A "step" = one pass of the hot path over one synthetic volume: n-link / t-link construction (mgc_build) + max-flow solve
 with image and markers already resident in HBM and the label array left in HBM (SURVEY.md 8(d) "headline,
@@ -17,7 +18,7 @@ Workloads (BASELINE.json `configs`; shapes are (Z, Y, X)):
     --strong                1024^3, 6-conn, cut into N slabs: the SAME volume at N = 1, 2, 4, 8 (strong scaling)
 
 The multi-GPU volume is a grid of 512^3 sphere blocks sharing one connected medium (only the outer faces of the whole
-volume are background); no CPU oracle reaches these sizes, so every N > 1 run ends with the device-side invariant check
+volume are background); no CPU oracle reaches these sizes, so every N > 1 run with --full ends with the device-side invariant check
 (mgc_validate over all slabs: conservation, no residual arc across the cut, no active excess, flow == cut) and FAILS if it
 does not hold.  After every relabel pass / colour phase the packed slab borders travel to the neighbour ranks with RCCL
 send/recv over xGMI (medpy_amd/slab.py); tiny all-reduces decide termination.  The launcher of the build contract
@@ -25,8 +26,17 @@ send/recv over xGMI (medpy_amd/slab.py); tiny all-reduces decide termination.  T
 a private directory of files (medpy_amd/rendezvous.py).
 
 Prints ONE JSON line (rank 0) with `roofline` (dominant kernel k_discharge_w, HIP-event timed on the launch stream inside
-the library) and `cpu_baseline` (the reference's own BK solver, compiled in place as oracle/_ref, timed on a bounded sample
-on the host cores; --cpu-full times the whole 512^3 instead, ~3 minutes and ~40 GB).
+the library during the timed steps).  A plain run does nothing else: set-up, warm-up, the timed steps, --dump-outputs, the line.
+
+--full adds what the headline figure does not need: the device-side invariant check (for N > 1 the run FAILS if it does not
+hold), the H2D / D2H timings, the label hash against the reference's, the parity record, the other single-GPU configs and the
+public API path (`also`, `api_end_to_end`; --no-extras drops them) and `cpu_baseline` (the reference's own BK solver, compiled
+in place as oracle/_ref, timed on the host cores; the whole 512^3 where the host has the memory, --no-cpu drops it).
+
+--dump-outputs DIR writes what the last timed step computed, as a caller of that path receives it: `flow.npy` (float64, one
+value), `labels_sample.npy` (float32, 1.0 = source side, at a fixed seeded sample of at most 8 Mi flat voxel indices; the whole
+volume when it is smaller) and `labels_per_plane.npy` (float64, the source-side count of every Z plane).  For N > 1 every rank
+writes its own slab's files with a `_rank<r>` suffix.
 """
 import argparse
 import hashlib
@@ -43,6 +53,7 @@ sys.path.insert(0, ROOT)
 B_ALG = {6: 71.0, 26: 231.0}  # algorithmic bytes per voxel, SURVEY.md 8(d): 4 + 2 + 2*(ndir/2*8 + 8) + 1; + 4 with a probability map
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md
 BLOCK = 512  # edge of one sphere block of the multi-GPU volume
+DUMP_VOXELS = 8 << 20  # --dump-outputs: label sample of all ranks together (float32: 32 MiB)
 
 
 def kernel_source_hash():
@@ -145,6 +156,19 @@ def cpu_baseline(n):
 def labels_sha256(labels):
     """the hash tests/golden/reference_large.json holds for the reference's label volumes (oracle/gen_golden.py large): SHA-256 of the packed bits"""
     return hashlib.sha256(np.packbits(np.asarray(labels).astype(np.uint8).ravel()).tobytes()).hexdigest()
+
+
+def dump_outputs(d, labels, flow, max_voxels=DUMP_VOXELS, suffix=""):
+    """--dump-outputs: the flow and the labels of the last timed step (module docstring); the same sample for the same shape"""
+    os.makedirs(d, exist_ok=True)
+    lab = np.asarray(labels)
+    flat = lab.reshape(-1)
+    if flat.size > max_voxels:
+        idx = np.sort(np.random.default_rng(0).integers(0, flat.size, max_voxels))
+        flat = flat[idx]
+    np.save(os.path.join(d, "flow%s.npy" % suffix), np.array([flow], dtype=np.float64))
+    np.save(os.path.join(d, "labels_sample%s.npy" % suffix), flat.astype(np.float32))
+    np.save(os.path.join(d, "labels_per_plane%s.npy" % suffix), lab.reshape(lab.shape[0], -1).sum(axis=1, dtype=np.float64))
 
 
 def golden_large():
@@ -306,11 +330,13 @@ def main():
     ap.add_argument("--xy", type=int, default=1024, help="cross-section edge of the multi-GPU volume (a multiple of --block)")
     ap.add_argument("--planes", type=int, default=256, help="planes per GPU of the multi-GPU volume")
     ap.add_argument("--block", type=int, default=BLOCK, help="edge of one sphere block of the multi-GPU volume")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write the flow and labels of the last timed step as .npy files into DIR")
+    ap.add_argument("--full", action="store_true", help="also the checks, comparisons, other configs and the CPU baseline (module docstring)")
     ap.add_argument("--cpu-sample", type=int, default=320)
     ap.add_argument("--cpu-full", action="store_true", help="(default when the host has the memory) the CPU leg runs the whole 512^3")
     ap.add_argument("--cpu-sample-only", action="store_true", help="CPU leg on the bounded sample whatever the host")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline only: no `also` (configs 2 / 3) and no `api_end_to_end` block (profiling runs)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full without `also` (configs 2 / 3) and `api_end_to_end`")
     ap.add_argument("--cpu-only", type=int, default=0, help=argparse.SUPPRESS)  # child process of cpu_baseline_in_run
     args = ap.parse_args()
     if args.cpu_only:
@@ -378,28 +404,32 @@ def main():
             for k in acc:
                 acc[k] += st[k]
         elapsed = time.perf_counter() - t0
-        t_d2h = time.perf_counter()
-        lab = g.labels()  # D2H of the label volume (one byte per voxel)
-        t_d2h = time.perf_counter() - t_d2h
-        fg_fraction = float(lab.mean())
-        h2d_bytes = s["image"].nbytes + s["fg"].size + s["bg"].size + (r["prob"].nbytes if regional else 0)
-        end_to_end = {"h2d_ms": round(t_h2d * 1e3, 2), "h2d_bytes": int(h2d_bytes), "d2h_ms": round(t_d2h * 1e3, 2), "d2h_bytes": int(lab.size),
-                      "note": "image + markers (+ probability map) from pageable host arrays into HBM (pinned staging, four host threads), labels back; outside the timed steps; never part of `value`"}
-        validation = g.validate()
-        _lib.assert_valid(validation)
-        t_h2d_cold = t_h2d  # (the first upload of the process also pins the staging buffers; the inputs go up once more, warm)
-        t_h2d = time.perf_counter()
-        g._set_boundary("difference_exponential", s["image"], s["sigma"], False)
-        g._set_markers(s["fg"], s["bg"])
-        if regional:
-            g._set_regional(r["prob"], r["alpha"])
-        t_h2d = time.perf_counter() - t_h2d
-        end_to_end["h2d_ms"], end_to_end["h2d_first_call_ms"] = round(t_h2d * 1e3, 2), round(t_h2d_cold * 1e3, 2)
-        head_sha = None
-        ref = golden_large().get("sphere_512_6") if (n == 512 and conn == 6 and not regional) else (golden_large().get("sphere_256_6") if (n == 256 and conn == 6 and not regional) else None)
-        if ref is not None:
-            head_sha = {"labels_sha256": labels_sha256(lab), "reference": ref["sha256_packed_labels"]}
-            head_sha["labels_match_reference"] = bool(head_sha["labels_sha256"] == head_sha["reference"])
+        fg_fraction = None
+        if args.full or args.dump_outputs:
+            t_d2h = time.perf_counter()
+            lab = g.labels()  # D2H of the label volume (one byte per voxel)
+            t_d2h = time.perf_counter() - t_d2h
+            fg_fraction = float(lab.mean())
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, lab, flow)
+        if args.full:
+            h2d_bytes = s["image"].nbytes + s["fg"].size + s["bg"].size + (r["prob"].nbytes if regional else 0)
+            end_to_end = {"h2d_ms": round(t_h2d * 1e3, 2), "h2d_bytes": int(h2d_bytes), "d2h_ms": round(t_d2h * 1e3, 2), "d2h_bytes": int(lab.size),
+                          "note": "image + markers (+ probability map) from pageable host arrays into HBM (pinned staging, four host threads), labels back; outside the timed steps; never part of `value`"}
+            validation = g.validate()
+            _lib.assert_valid(validation)
+            t_h2d_cold = t_h2d  # (the first upload of the process also pins the staging buffers; the inputs go up once more, warm)
+            t_h2d = time.perf_counter()
+            g._set_boundary("difference_exponential", s["image"], s["sigma"], False)
+            g._set_markers(s["fg"], s["bg"])
+            if regional:
+                g._set_regional(r["prob"], r["alpha"])
+            t_h2d = time.perf_counter() - t_h2d
+            end_to_end["h2d_ms"], end_to_end["h2d_first_call_ms"] = round(t_h2d * 1e3, 2), round(t_h2d_cold * 1e3, 2)
+            ref = golden_large().get("sphere_512_6") if (n == 512 and conn == 6 and not regional) else (golden_large().get("sphere_256_6") if (n == 256 and conn == 6 and not regional) else None)
+            if ref is not None:
+                head_sha = {"labels_sha256": labels_sha256(lab), "reference": ref["sha256_packed_labels"]}
+                head_sha["labels_match_reference"] = bool(head_sha["labels_sha256"] == head_sha["reference"])
         g.close()
         gshape = shape
         workload = "%d^3 sphere volume (float32), %d-conn, boundary_difference_exponential sigma=15%s, fg=inner ball, bg=6 faces" % (
@@ -493,11 +523,16 @@ def main():
             t = store.allreduce([elapsed] + step_s, "max")  # a step ends when its slowest rank is done (every exchange synchronises neighbours)
             elapsed, step_s = float(t[0]), [float(v) for v in t[1:]]
         flow = float(ex.allreduce_sum([part]))
-        lab, _ = slab.finish()
-        fg_fraction = float(ex.allreduce_sum([float(lab.sum())])) / float(np.prod(gshape))
-        validation = validate_slabs([slab], ex)  # no oracle reaches this size: the invariants are the check
-        _lib.assert_valid(validation)
-        assert abs((validation["cut_capacity"] + validation["flow_constant"]) - flow) <= 1e-9 * max(abs(flow), 1e-300)
+        fg_fraction = None
+        if args.full or args.dump_outputs:  # (the same on every rank: the reductions below are collective)
+            lab, _ = slab.finish()
+            fg_fraction = float(ex.allreduce_sum([float(lab.sum())])) / float(np.prod(gshape))
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, lab, flow, DUMP_VOXELS // world, "_rank%d" % rank if world > 1 else "")
+        if args.full:
+            validation = validate_slabs([slab], ex)  # no oracle reaches this size: the invariants are the check
+            _lib.assert_valid(validation)
+            assert abs((validation["cut_capacity"] + validation["flow_constant"]) - flow) <= 1e-9 * max(abs(flow), 1e-300)
         if world > 1:
             store.barrier()
         workload = "%dx%dx%d volume (%dx%dx%d sphere blocks of %d^3, float32, one connected medium), %d-conn, boundary_difference_exponential sigma=15, bg=outer faces" % (
@@ -521,7 +556,7 @@ def main():
                        "baseline_config": args.config or (None if args.strong else {1: "headline", 4: 4}.get(world)),
                        "parallelism": ("%d exact Z-slabs (one per GPU, %d planes each), halo exchange between neighbour slabs" % (
                            world, gshape[0] // world)) if world > 1 else "single GPU",
-                       "transport": transport, "fg_fraction": round(fg_fraction, 5), "flow": flow},
+                       "transport": transport, "fg_fraction": None if fg_fraction is None else round(fg_fraction, 5), "flow": flow},
             "job_roofline_frac": round(value * 1e6 / world * b_alg / (HBM_PEAK_GBS * 1e9), 6),
             "per_gpu_algorithmic_gbs": round(value * 1e6 / world * b_alg / 1e9, 2),
             "validation": validation,
@@ -574,8 +609,9 @@ def main():
                                              "RCCL); this run drove the schedule from Python over the development transport")
         if world == 1 and not args.strong and head_sha is not None:
             out["config"].update(head_sha)
-        out["parity"] = parity_relaxation_summary()
-        if world == 1 and not args.config and not args.strong and not args.no_extras and not args.size:
+        if args.full:
+            out["parity"] = parity_relaxation_summary()
+        if args.full and world == 1 and not args.config and not args.strong and not args.no_extras and not args.size:
             # the other single-GPU BASELINE configs and the public API path, inside the driver's run
             out["api_end_to_end"] = api_end_to_end()
             out["also"] = {"config2": also_case("config2", 256, 6, False, golden_key="sphere_256_6"),
@@ -587,7 +623,7 @@ def main():
                            "ties": also_case("ties", 512, 6, False, steps=2, warmup=0, workload="ties"),
                            "conn26_markers": also_case("conn26_markers", 512, 26, False, steps=2, warmup=0),
                            "ct_uint16": also_case("ct_uint16", 512, 6, False, steps=2, workload="ct")}
-        if not args.no_cpu and world == 1 and not args.config and not args.strong:
+        if args.full and not args.no_cpu and world == 1 and not args.config and not args.strong:
             out["cpu_baseline"] = cpu_baseline_in_run(args.cpu_sample, not args.cpu_sample_only)
         else:
             out["cpu_baseline"] = None

@@ -1,6 +1,6 @@
 """Generate tests/golden/*.npz by running the REFERENCE ITSELF in this container.
 
-    python -m oracle.gen_golden            (needs /root/reference; see oracle/overlay.py)
+    python -m oracle.gen_golden [b0 | large | labels | oracle]      (needs the reference's sources; see oracle/overlay.py)
 
 Every fixture stores inputs plus what the reference's own code produced for them:
 ``medpy.graphcut.graph_from_voxels`` (generate.py:33-174) with the reference energy terms
@@ -303,8 +303,86 @@ def main_large():
         json.dump(store, open(path, "w"), indent=1, sort_keys=True)
 
 
+def oracle_graphs():
+    """the random graphs tests/test_oracle_port_vs_ref.py solves (seed 7): (n, i, j, cap, rev, src, snk)"""
+    rng = np.random.default_rng(7)
+    out = []
+    for trial in range(400):
+        n = int(rng.integers(2, 60)); m = int(rng.integers(0, 300))
+        i = rng.integers(0, n, m); j = rng.integers(0, n, m)
+        keep = i != j; i, j = i[keep], j[keep]
+        if trial % 3 == 0:  # tie-heavy integers, zero reverse capacities
+            cap = rng.integers(1, 5, i.size).astype(float); rev = rng.integers(0, 5, i.size).astype(float)
+        else:  # 25 decades of dynamic range
+            cap = rng.random(i.size) * 10.0 ** rng.integers(-20, 5, i.size); rev = rng.random(i.size)
+        src = rng.random(n) * (rng.random(n) < 0.3) * 65535 ** (trial % 2)
+        snk = rng.random(n) * (rng.random(n) < 0.3)
+        out.append((n, i, j, cap, rev, src, snk))
+    return out
+
+
+ORACLE_LATTICES = [("sphere", (40, 40, 40)), ("hard", (32, 32, 32)), ("ties", (28, 28, 28)), ("sphere", (9, 33, 17))]
+
+
+def lattice_key(gen, shape):
+    return "%s_%s" % (gen, "x".join(str(v) for v in shape))
+
+
+def parallel_arc_calls(kind):
+    """the calls of tests/test_gpu_labels.py::test_parallel_arcs_like_the_compiled_reference (seed 3 + kind): 400 add_edge /
+    sum_edge calls between 30 nodes, then the t-link capacities; returns (n, calls, src, snk)"""
+    rng = np.random.default_rng(3 + kind)
+    n = 30
+    calls = []
+    for k in range(400):
+        a, b = (int(v) for v in rng.choice(n, 2, replace=False))
+        c, r = (float(v) for v in rng.integers(0, 9, 2)) if kind else (float(rng.random()), float(rng.random()))
+        which = "add" if rng.random() < 0.5 else "sum"
+        calls.append((which, a, b, c, r))
+    src = np.where(rng.random(n) < 0.3, rng.integers(1, 20, n), 0).astype(float)
+    snk = np.where(rng.random(n) < 0.3, rng.integers(1, 20, n), 0).astype(float)
+    return n, calls, src, snk
+
+
+def main_oracle():
+    """What the compiled reference BK (oracle/_ref/libbkref.so) gives for the graphs the checker tests drive it through:
+    oracle_graphs(), ORACLE_LATTICES and parallel_arc_calls() -> reference_oracle.npz"""
+    from medpy_amd import synthetic
+    from oracle import bk, pipeline
+    assert bk.available("ref"), "needs the compiled reference (oracle/_ref): run where the reference's sources are (oracle/Makefile)"
+    store = {}
+    for t, (n, i, j, cap, rev, src, snk) in enumerate(oracle_graphs()):
+        g = bk.BKGraph(n, max(len(i), 1), "ref")
+        if len(i):
+            g.sum_edges(i, j, cap, rev)
+        g.add_tweights(None, src, snk)
+        key = "graph%03d" % t
+        store[key + "/flow"] = g.maxflow()
+        store[key + "/labels"] = g.labels()
+        store[key + "/trcap"] = np.array([g.get_trcap(k) for k in range(n)])
+        store[key + "/arc_num"] = g.get_arc_num()
+    for gen, shape in ORACLE_LATTICES:
+        s = getattr(synthetic, gen)(shape)
+        cut = pipeline.graphcut_voxel(s["fg"], s["bg"], kind="ref", term=s["term"], image=s["image"], sigma=s["sigma"])
+        store[lattice_key(gen, shape) + "/flow"], store[lattice_key(gen, shape) + "/labels"] = cut.flow, cut.labels
+    for kind in (0, 1, 2):
+        n, calls, src, snk = parallel_arc_calls(kind)
+        o = bk.BKGraph(n, 16, "ref")
+        for which, a, b, c, r in calls:
+            (o.add_edges if which == "add" else o.sum_edges)([a], [b], [c], [r])
+        key = "parallel_arcs%d" % kind
+        store[key + "/edges"] = np.array([[o.get_edge(a, b) if a != b else 0.0 for b in range(n)] for a in range(n)])
+        o.add_tweights(None, src, snk)
+        store[key + "/flow"] = o.maxflow()
+        store[key + "/labels"] = o.labels()
+    np.savez_compressed(os.path.join(OUT, "reference_oracle.npz"), **store)
+    print("reference_oracle.npz", os.path.getsize(os.path.join(OUT, "reference_oracle.npz")))
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "b0":
+    if len(sys.argv) > 1 and sys.argv[1] == "oracle":
+        main_oracle()
+    elif len(sys.argv) > 1 and sys.argv[1] == "b0":
         main_b0()
     elif len(sys.argv) > 1 and sys.argv[1] == "large":
         main_large()

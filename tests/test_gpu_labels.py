@@ -240,43 +240,35 @@ def test_get_edge_kat_of_the_reference(kind):
         assert isinstance(g.get_edge(0, 1), int)
 
 
-@pytest.mark.skipif(not bk.available("ref"), reason="oracle/_ref not built")
 @pytest.mark.parametrize("kind", [0, 1, 2])
 def test_parallel_arcs_like_the_compiled_reference(kind):
     """add_edge creates PARALLEL arcs (graph.h:428-454): get_edge reports the pair added last (the first the list walk meets,
     graph.h:500-509), sum_edge adds to that pair, and the flow sees the sum of all of them -- every read-back and the cut
-    compared with the unmodified reference driven through the same calls"""
+    compared with what the unmodified reference gave for the same calls (tests/golden/reference_oracle.npz, oracle/gen_golden.py)"""
+    from oracle.gen_golden import parallel_arc_calls
     G = _graph_types()[kind]
-    rng = np.random.default_rng(3 + kind)
-    n = 30
-    o = bk.BKGraph(n, 16, "ref")
+    ref = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_oracle.npz"))
+    key = "parallel_arcs%d/" % kind
+    n, calls, src, snk = parallel_arc_calls(kind)
     g = G(n, 16)
     assert g.add_node(n) == 0
-    calls = []
-    for k in range(400):
-        a, b = (int(v) for v in rng.choice(n, 2, replace=False))
-        c, r = (float(v) for v in rng.integers(0, 9, 2)) if kind else (float(rng.random()), float(rng.random()))
-        which = "add" if rng.random() < 0.5 else "sum"
-        calls.append((which, a, b, c, r))
     for which, a, b, c, r in calls:
         cc, rr = (int(c), int(r)) if kind == 2 else (c, r)
         if which == "add":
-            o.add_edges([a], [b], [c], [r]); g.add_edge(a, b, cc, rr)
+            g.add_edge(a, b, cc, rr)
         else:
-            o.sum_edges([a], [b], [c], [r]); g.sum_edge(a, b, cc, rr)
+            g.sum_edge(a, b, cc, rr)
+    edges = ref[key + "edges"]
     for a in range(n):
         for b in range(n):
             if a != b:
-                assert g.get_edge(a, b) == o.get_edge(a, b), (a, b)
-    src = np.where(rng.random(n) < 0.3, rng.integers(1, 20, n), 0).astype(float)
-    snk = np.where(rng.random(n) < 0.3, rng.integers(1, 20, n), 0).astype(float)
-    o.add_tweights(None, src, snk)
+                assert g.get_edge(a, b) == edges[a, b], (a, b)
     for u in range(n):
         if src[u] or snk[u]:
             g.add_tweights(u, int(src[u]) if kind == 2 else float(src[u]), int(snk[u]) if kind == 2 else float(snk[u]))
-    oflow, flow = o.maxflow(), g.maxflow()
-    assert flow == pytest.approx(oflow, rel=1e-6 if kind == 1 else 1e-12)
-    np.testing.assert_array_equal(g.labels().astype(np.uint8), o.labels())  # the minimal sink set is unique, ties or not
+    flow = g.maxflow()
+    assert flow == pytest.approx(float(ref[key + "flow"]), rel=1e-6 if kind == 1 else 1e-12)
+    np.testing.assert_array_equal(g.labels().astype(np.uint8), ref[key + "labels"])  # the minimal sink set is unique, ties or not
 
 
 def test_reset_returns_an_empty_graph():

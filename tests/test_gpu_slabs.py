@@ -230,7 +230,7 @@ def test_bench_multi_gpu_code_path_at_reduced_size(flags, conn):
     contract's, bench.py itself imports no PyTorch), at a reduced size and with the development transport (two ranks share the
     one GPU of this box, borders through host buffers and the file store): the workload
     generator (grid of sphere blocks, outer shell = background), the slab build, the distributed schedule, the
-    device-side invariant check over all slabs that every N > 1 run ends with -- for the default (6-conn, config 4's
+    device-side invariant check over all slabs that every N > 1 run with --full ends with -- for the default (6-conn, config 4's
     family), --config 5 (26-conn) and --strong."""
     import json
     import os
@@ -240,7 +240,7 @@ def test_bench_multi_gpu_code_path_at_reduced_size(flags, conn):
     env = dict(os.environ, MEDPY_DIST_BACKEND="host", MEDPY_BENCH_ANY_WORLD="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29713", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--xy", "64",
-           "--planes", "32", "--block", "32"] + flags
+           "--planes", "32", "--block", "32", "--full"] + flags
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert res.returncode == 0, (res.stdout[-3000:], res.stderr[-3000:])
     line = [ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1]
@@ -260,6 +260,31 @@ def test_bench_multi_gpu_code_path_at_reduced_size(flags, conn):
                                    boundary_term_args=(img, 15.0, False), **({"connectivity": 26} if conn == 26 else {}))
     assert out["config"]["flow"] == pytest.approx(g.maxflow(), rel=1e-9)
     assert out["config"]["fg_fraction"] == pytest.approx(float(g.labels().mean()), abs=1e-5)
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """bench.py --gpus 1 without --full at a reduced size: the result line times exactly --steps steps, and --dump-outputs writes
+    the flow and labels of the timed path (float32 / float64) that the same volume gives on one handle"""
+    import json
+    import os
+    import subprocess
+    import sys
+    from medpy_amd import synthetic
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--size", "64",
+           "--dump-outputs", str(tmp_path)]
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+    assert res.returncode == 0, (res.stdout[-3000:], res.stderr[-3000:])
+    out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["steps"] == 3 and len(out["step_ms"]) == 3 and out["ms_per_step"] > 0
+    assert out["unit"] == "Mvoxels/s" and out["higher_is_better"] is True and out["dtype"] == "f64"
+    assert out["cpu_baseline"] is None and "also" not in out and out["validation"] is None
+    labels, flow = _single(synthetic.sphere((64, 64, 64), seed=0))
+    f, sample, planes = (np.load(str(tmp_path / n)) for n in ("flow.npy", "labels_sample.npy", "labels_per_plane.npy"))
+    assert f.dtype == np.float64 and sample.dtype == np.float32 and planes.dtype == np.float64
+    assert f[0] == pytest.approx(flow, rel=1e-9) and f[0] == out["config"]["flow"]
+    np.testing.assert_array_equal(sample, labels.reshape(-1).astype(np.float32))  # 64^3 is below the sample size: every voxel
+    np.testing.assert_array_equal(planes, labels.sum(axis=(1, 2)))
 
 
 def test_two_slabs_give_the_single_handle_labels_at_bench_size():

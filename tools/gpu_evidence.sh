@@ -50,7 +50,7 @@ print("dispatches in the step: %d; gaps > 5 us: %d, > 20 us: %d; idle between di
 PY
     ;;
   bench)
-    python bench.py 2> $G/${TAG}_bench.err | tail -1 > $G/${TAG}_bench_n1.json; cut -c1-900 $G/${TAG}_bench_n1.json ;;
+    python bench.py --full 2> $G/${TAG}_bench.err | tail -1 > $G/${TAG}_bench_n1.json; cut -c1-900 $G/${TAG}_bench_n1.json ;;
   config3)
     OUT=$ROOT/$G/prof26; rm -rf $OUT; mkdir -p $OUT; ( cd /tmp; export TMPDIR=/tmp
       timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -- python $ROOT/bench.py --config 3 --no-cpu --no-extras --steps 2 --warmup 1 > $OUT/trace.log 2>&1
@@ -62,7 +62,7 @@ PY
     [ -n "$W" ] && python tools/rocpd_summary.py pmc $W > $G/${TAG}_config3_write.csv
     [ -n "$F" ] && [ -n "$W" ] && python tools/rocpd_summary.py json $F $W k26_discharge_w > $G/pmc_discharge26.json && cp $G/pmc_discharge26.json profiles/
     rm -rf $OUT
-    python bench.py --config 3 --no-cpu --no-extras 2>> $G/${TAG}_bench.err | tail -1 > $G/${TAG}_bench_config3.json; cut -c1-400 $G/${TAG}_bench_config3.json ;;
+    python bench.py --config 3 --full --no-cpu --no-extras 2>> $G/${TAG}_bench.err | tail -1 > $G/${TAG}_bench_config3.json; cut -c1-400 $G/${TAG}_bench_config3.json ;;
   workloads)
     timeout 400 python tools/gpu_workloads.py 512 > $G/${TAG}_workloads.jsonl 2>&1
     ( timeout 300 python tools/gpu_ab.py --n 512 --conn 26 --reps 2 base; timeout 300 python tools/gpu_ab.py --n 512 --conn 26 --regional --reps 2 base prepush=0
