@@ -79,6 +79,7 @@ typedef struct mgc_stats {
     int64_t discharge_wave_launches;
     int64_t discharge_wave_tiles;
     int64_t timing_stride;     /* every n-th solver launch of a kind carries a HIP event pair; the _ms are their mean x launches */
+    double  update_ms;         /* device time of the last t-link update (mgc_update_*): k_update_tlinks + its flow-constant sum; 0 after mgc_build */
 } mgc_stats;
 
 /* Invariants of a maximum preflow, checked on the device (mgc_validate).  The reference has the same idea as a debugging
@@ -151,6 +152,16 @@ int mgc_set_regional_probability(mgc_handle h, const void* probability_map, int 
 /* Replaces set_source_nodes / set_sink_nodes over marker masks (generate.py:169-172,
  * graph.py:310-380): nonzero fg -> add_tweights(i, 65535, 0), nonzero bg -> add_tweights(i, 0, 65535). */
 int mgc_set_markers(mgc_handle h, const uint8_t* fg, const uint8_t* bg);
+
+/* WARM UPDATES of a built handle (the interactive loop: a stroke is added, the graph is cut again).  They replace the markers /
+ * the regional term as mgc_set_markers / mgc_set_regional_probability do, but keep the residual graph in HBM: the n-links are
+ * not touched, the new t-links are folded into the residual state, and the next mgc_maxflow continues from it.  Its
+ * labels, flow and mgc_validate are those of mgc_build + mgc_maxflow of the same inputs (explicit merged t-links and plug-in
+ * edges of the build included, unchanged).  Valid on a built handle before or after mgc_maxflow; MGC_ERR_STATE before
+ * mgc_build, after a solve that returned MGC_ERR_NOT_CONVERGED, and on a slab handle.  mgc_set_markers /
+ * mgc_set_regional_probability + mgc_build remain the cold rebuild. */
+int mgc_update_markers(mgc_handle h, const uint8_t* fg, const uint8_t* bg);
+int mgc_update_regional_probability(mgc_handle h, const void* probability_map, int dtype, double alpha);
 
 /* After mgc_maxflow (or the slab driver's last step): see mgc_validation.  Also works on a graph whose solve was cut
  * short (MGC_ERR_NOT_CONVERGED): it then reports the excess that is still active.  MGC_ERR_STATE before the first solve

@@ -32,7 +32,7 @@ class Stats(C.Structure):
         ("relabel_tiles", C.c_int64), ("global_relabels", C.c_int64), ("phases", C.c_int64), ("ntiles", C.c_int64),
         ("nvox", C.c_int64), ("device_bytes", C.c_int64), ("reserved", C.c_int64 * 3),
         ("discharge_wave_ms", C.c_double), ("discharge_wave_launches", C.c_int64), ("discharge_wave_tiles", C.c_int64),
-        ("timing_stride", C.c_int64),
+        ("timing_stride", C.c_int64), ("update_ms", C.c_double),
     ]
 
     def as_dict(self):
@@ -122,6 +122,8 @@ SIGNATURES = {
     "mgc_set_boundary_lut": (_INT, [_VP, _VP, _I64]),
     "mgc_set_regional_probability": (_INT, [_VP, _VP, _INT, _DBL]),
     "mgc_set_markers": (_INT, [_VP, _VP, _VP]),
+    "mgc_update_markers": (_INT, [_VP, _VP, _VP]),
+    "mgc_update_regional_probability": (_INT, [_VP, _VP, _INT, _DBL]),
     "mgc_add_edges": (_INT, [_VP, _I64, _VP, _VP, _VP, _VP]),
     "mgc_set_tweights_merged": (_INT, [_VP, _VP, _DBL]),
     "mgc_build": (_INT, [_VP]),

@@ -1203,6 +1203,45 @@ __device__ __forceinline__ double mgc_block_sum(double v, double* scratch)
     return scratch[0];
 }
 
+/* The merged t-link of voxel `id` (C order) from the inputs resident in HBM, in the reference's call order: explicit merged t-links,
+ * the regional term in the map's dtype, then the fg and bg markers (generate.py:159-172).  fc collects the voxel's share of the flow
+ * constant.  One body for k_build and k_update_tlinks: a warm update merges bit for bit what a cold build of the same inputs does.
+ * AP: a pointer to MgcBuildArgs in any address space (k_build reads its arguments through the kernarg segment, mgc_kernarg_again). */
+template <class AP>
+__device__ __forceinline__ void mgc_merge_tlinks(AP At, int64_t id, uint32_t fg, uint32_t bg, double& tr, double& fc)
+{
+    if (At->tr_in) tr = At->tr_in[id];
+    if (At->prob) {
+        double cs, ck;
+        if (At->prob_dtype == MGC_F32) {
+            const float p = ((const float*)At->prob)[id], al = (float)At->alpha;
+            cs = (double)(p * al);
+            ck = (double)((1.0f - p) * al);
+        } else {
+            const double p = ((const double*)At->prob)[id];
+            cs = p * At->alpha;
+            ck = (1.0 - p) * At->alpha;
+        }
+        mgc_add_tweights(tr, fc, cs, ck);
+    }
+    if (fg) mgc_add_tweights(tr, fc, MGC_MARKER_MAX, 0.0);
+    if (bg) mgc_add_tweights(tr, fc, 0.0, MGC_MARKER_MAX);
+}
+
+/* The tile's partial of the flow constant (summed over the tiles by mgc_sum_partials).  Only voxels whose t-links were merged more
+ * than once contribute (regional term + marker, fg and bg marker on one voxel): most tiles skip the ten barriers of the tree sum.
+ * t: the lane (threadIdx.x); any_fc: some lane of the workgroup has fc != 0 (uniform). */
+__device__ __forceinline__ void mgc_flow_const_partial(const MgcLattice& L, int tile, int t, double fc, bool any_fc, double* scratch, double* fpart)
+{
+    if (any_fc) {
+        const double s = mgc_block_sum(fc, scratch);
+        if (t == 0) fpart[tile] = mgc_owned(L, tile) ? s : 0.0;
+        __syncthreads();
+    } else if (t == 0) {
+        fpart[tile] = 0.0;
+    }
+}
+
 /* A kernel's own arguments, read AGAIN where they are used.  The twenty-odd pointers of k_build's two argument structs are loop invariants: the
  * optimiser loads them once in front of the tile loop and keeps them -- more scalar registers than the wave has, so they went to and fro between
  * SGPRs and lanes of a VGPR around every use (65 - 70 spilled registers, ~150 v_readlane / v_writelane per tile).  A pointer to the kernarg segment
@@ -1333,24 +1372,7 @@ __device__ __forceinline__ void k_build_tiles(const MgcLattice& L, const MgcBuil
              * behind the load, and the wait that goes with it -- at the top of the tile -- is a wait for the stores of the tile before */
             asm volatile("" : "+v"(pre_fg), "+v"(pre_bg));
             const MGC_KARG MgcBuildArgs* const At = mgc_kernarg_again<MgcBuildArgs>(MGC_BUILD_ARGS_OFFSET);
-            if (valid) {
-                if (At->tr_in) tr = At->tr_in[id];
-                if (At->prob) {
-                    double cs, ck;
-                    if (At->prob_dtype == MGC_F32) {
-                        const float p = ((const float*)At->prob)[id], al = (float)At->alpha;
-                        cs = (double)(p * al);
-                        ck = (double)((1.0f - p) * al);
-                    } else {
-                        const double p = ((const double*)At->prob)[id];
-                        cs = p * At->alpha;
-                        ck = (1.0 - p) * At->alpha;
-                    }
-                    mgc_add_tweights(tr, fc, cs, ck);
-                }
-                if (pre_fg) mgc_add_tweights(tr, fc, MGC_MARKER_MAX, 0.0);
-                if (pre_bg) mgc_add_tweights(tr, fc, 0.0, MGC_MARKER_MAX);
-            }
+            if (valid) mgc_merge_tlinks(At, id, pre_fg, pre_bg, tr, fc);
         };
         auto vote = [&]() __attribute__((always_inline)) {
             const int bits = (__ballot(tr < 0.0) != 0ull ? 2 : 0) | (__ballot(tr > 0.0) != 0ull ? 1 : 0) | (__ballot(fc != 0.0) != 0ull ? 4 : 0);
@@ -1676,15 +1698,7 @@ __device__ __forceinline__ void k_build_tiles(const MgcLattice& L, const MgcBuil
             sink_tiles += any_sink ? 1 : 0;
             wall_tiles += weak_voxels >= MGC_WALL_VOXELS ? 1 : 0;
         }
-        /* flow constant: only voxels whose t-links were merged more than once contribute (regional term + marker, fg and bg
-         * marker on one voxel): most tiles skip the ten barriers of the tree sum */
-        if (tbits & 4) { /* uniform */
-            const double s = mgc_block_sum(fc, scratch);
-            if (t == 0) As->fpart[tile] = mgc_owned(L, tile) ? s : 0.0;
-            __syncthreads();
-        } else if (t == 0) {
-            As->fpart[tile] = 0.0;
-        }
+        mgc_flow_const_partial(L, tile, t, fc, (tbits & 4) != 0, scratch, As->fpart);
         if constexpr (FULL) __syncthreads(); /* the weights above read the image tile in LDS, the next tile's load overwrites it (the
                                                 6-neighbourhood path has its vote barrier behind the weights) */
         if (has_next) stage_f32(t); /* everybody is past this tile's reads of the block; this tile's stores are still on their way */
@@ -1805,6 +1819,90 @@ __global__ __launch_bounds__(MGC_TV) void k_refresh_mask(MgcLattice L)
         if (L.ndir == 6) L.rmask[(int64_t)tile * MGC_TV + t] = (uint8_t)(m | (snk ? MGC_MASK_SINK : 0));
         else L.rmask32[(int64_t)tile * MGC_TV + t] = m | (snk ? MGC26_MASK_SINK : 0u);
     }
+}
+
+/* ======================================================================================
+ * warm update of the t-links (mgc_update_markers / mgc_update_regional_probability)
+ * ==================================================================================== */
+/* Every voxel gets the t-link the inputs resident now merge to (mgc_merge_tlinks, the body k_build runs), and the change is folded
+ * into the residual state as a SIGNED EXCESS: with x = excess - sink,  x' = x + (tr' - tr0),  excess = max(x', 0),  sink = max(-x', 0),
+ * tr0 = tr'.  At every moment of a solve  excess - sink = tr0 + (net n-link inflow)  (what k_validate checks), so the new state keeps
+ * that identity for tr'.  Per voxel this raises the source and the sink capacity by one amount: every cut moves by the same constant,
+ * the minimum cuts and the minimal sink side among them stay, and the cut value -- read from the labels, tr0 and the capacities as
+ * built -- is the one a cold build of the same inputs gives.  No flow has to be pulled back; n-links are not touched.
+ * Voxels whose t-link did not change keep their state bit for bit.
+ *
+ * FLAGS.  The 6-neighbourhood writes the planes tr0 and sink only where a tile's flags say somebody reads them (k_build), and every
+ * reader -- discharges, k_cut_value6 / 26, k_validate, k_untile_f64 -- goes by the same rule:
+ *   tflags bit 0: some voxel has tr0 > 0;  bit 1: some voxel has tr0 < 0 OR a residual sink link (sink > 0);
+ *   tr0 is valid for the whole tile where tflags != 0, sink where bit 1 is set;  status MGC_ST_SINK: some sink > 0 (the discharges
+ *   read the sink plane only under it, so elsewhere the residual sink links are 0 whatever the plane holds).
+ * A build only ever has sink > 0 where tr0 < 0; after a solve a voxel whose flow left through its n-links can be left with sink > 0
+ * under tr0' >= 0 when it loses a source marker -- hence the second half of bit 1.  A tile without flags holds garbage in both planes:
+ * it is read as 0 and written in full when the tile gains a flag.
+ * The status word is rewritten as k_build writes it (SINK / EXCESS / SOURCE; DIRTY, SUSPECT, ALLINF, SETTLED and the support bits
+ * cleared), the stamps are cleared: the next mgc_solve starts like the first one of a build, from a global relabel from scratch. */
+template <bool FULL>
+__global__ __launch_bounds__(MGC_TV) void k_update_tlinks(MgcLattice L, MgcBuildArgs A)
+{
+    __shared__ double scratch[MGC_TV];
+    __shared__ int vote;
+    const int t = threadIdx.x;
+    const int lz = t >> 6, ly = (t >> 3) & 7, lx = t & 7;
+    int flagged_sink = 0; /* (thread 0) tiles with tflags bit 1 */
+    for (int tile = blockIdx.x; tile < L.ntiles; tile += gridDim.x) {
+        if (t == 0) vote = 0;
+        int tz, ty, tx;
+        mgc_tile_coords(L, tile, tz, ty, tx);
+        const int64_t gz = (int64_t)tz * 8 + lz, gy = (int64_t)ty * 8 + ly, gx = (int64_t)tx * 8 + lx;
+        const int64_t v = (int64_t)tile * MGC_TV + t;
+        const uint32_t st = L.status[tile];
+        const uint32_t tf_old = A.tflags[tile];
+        double tr = 0.0, fc = 0.0;
+        if (gz < L.dz && gy < L.dy && gx < L.dx) {
+            const int64_t id = (gz * L.dy + gy) * L.dx + gx;
+            mgc_merge_tlinks(&A, id, A.fg ? A.fg[id] : 0u, A.bg ? A.bg[id] : 0u, tr, fc);
+        }
+        const bool tr0_ok = FULL || tf_old != 0u, sink_ok = FULL || (st & MGC_ST_SINK) != 0u;
+        const double tr_old = tr0_ok ? A.tr0[v] : 0.0;
+        const double sk_old = sink_ok ? L.sink[v] : 0.0;
+        double e = L.excess[v], sk = sk_old;
+        const bool changed = tr != tr_old;
+        if (changed) {
+            const double x = (e - sk) + (tr - tr_old);
+            e = x > 0.0 ? x : 0.0;
+            sk = x < 0.0 ? -x : 0.0;
+        }
+        __syncthreads(); /* (the reset of the vote word, before the votes) */
+        const int bits = (__ballot(tr > 0.0) ? 1 : 0) | (__ballot(tr < 0.0 || sk > 0.0) ? 2 : 0) | (__ballot(e > 0.0) ? 4 : 0) |
+                         (__ballot(sk > 0.0) ? 8 : 0) | (__ballot(fc != 0.0) ? 16 : 0);
+        if ((t & 63) == 0 && bits) atomicOr(&vote, bits);
+        __syncthreads();
+        const int tb = vote;
+        const uint32_t tf_new = (uint32_t)tb & 3u;
+        if (!FULL) {
+            if (tf_new != 0u && (!tr0_ok || changed)) A.tr0[v] = tr;
+            if ((tf_new & 2u) && (!sink_ok || sk != sk_old)) L.sink[v] = sk;
+        } else if (changed) {
+            A.tr0[v] = tr;
+            L.sink[v] = sk;
+        }
+        if (changed) L.excess[v] = e;
+        if ((sk > 0.0) != (sk_old > 0.0)) { /* (elsewhere the sink bit of the mask, sk_old > 0, stands) */
+            if (FULL) L.rmask32[v] = (L.rmask32[v] & ~MGC26_MASK_SINK) | (sk > 0.0 ? MGC26_MASK_SINK : 0u);
+            else L.rmask[v] = (uint8_t)((L.rmask[v] & ~MGC_MASK_SINK) | (sk > 0.0 ? MGC_MASK_SINK : 0));
+        }
+        if (t == 0) {
+            L.status[tile] = ((tb & 8) ? MGC_ST_SINK : 0u) | ((tb & 4) ? MGC_ST_EXCESS : 0u) | ((!FULL && (tb & 1)) ? MGC_ST_SOURCE : 0u);
+            A.tflags[tile] = (uint8_t)tf_new;
+            L.stamp[tile] = 0;
+            L.rstamp[tile] = 0;
+            flagged_sink += (tf_new & 2u) ? 1 : 0;
+        }
+        mgc_flow_const_partial(L, tile, t, fc, (tb & 16) != 0, scratch, A.fpart);
+        __syncthreads(); /* everybody has read the vote word before the next tile resets it */
+    }
+    if (!FULL && t == 0 && flagged_sink) atomicAdd(&L.count[MGC_CNT_SINK_TILES], flagged_sink);
 }
 
 /* ======================================================================================
@@ -2516,6 +2614,7 @@ struct mgc_graph {
     double* h_scalar = nullptr; /* pinned */
     uint8_t* h_labels = nullptr; bool labels_on_host = false;
     bool built = false, solved = false;
+    bool unconverged = false;  /* the last solve of this build stopped at MGC_ERR_NOT_CONVERGED: warm updates are refused until the next mgc_build */
     bool labels_valid = false; /* the distance labels belong to this build (set by the first label fill of a solve, cleared by mgc_build) */
     void* d_vout = nullptr;    /* MgcValidateOut of mgc_validate */
     uint16_t* d_dt16 = nullptr; /* scratch of the distance-transform relabel (uint16 per voxel, tile-major), allocated on first use */
@@ -4122,6 +4221,81 @@ int mgc_set_tweights_merged(mgc_handle h, const double* tr, double flow_const)
     return mgc_upload(h, (void**)&h->d_tr_in, tr, (size_t)h->nvox * sizeof(double));
 }
 
+/* ---- warm updates of the t-links: the residual state of the handle stays, k_update_tlinks folds the new t-links in ---- */
+static int mgc_update_check(mgc_handle h, const char* what)
+{
+    if (!h->built) return mgc_fail(h, MGC_ERR_STATE, "%s before mgc_build", what);
+    if (h->nranks > 1) return mgc_fail(h, MGC_ERR_STATE, "%s: a slab of a multi-GPU volume is rebuilt, not updated", what);
+    if (h->unconverged) return mgc_fail(h, MGC_ERR_STATE, "%s after a solve that did not converge: rebuild (mgc_build)", what);
+    return MGC_OK;
+}
+
+static int mgc_update_tlinks(mgc_handle h)
+{
+    MgcRange range_("mgc_update_tlinks");
+    MgcLattice& L = h->L;
+    MgcBuildArgs& A = h->build_args; /* (the readers of the cut value and the invariants take the inputs from here too) */
+    A.prob = h->d_prob; A.prob_dtype = h->prob_dtype; A.alpha = h->alpha;
+    A.fg = h->d_fg; A.bg = h->d_bg;
+    const int grid = L.ntiles < h->grid_cap * 4 ? L.ntiles : h->grid_cap * 4;
+    MGC_HIP(h, hipEventRecord(h->ev[0], h->stream));
+    /* the counters start from zero as after mgc_build (k_update_tlinks counts the sink tiles) */
+    MGC_HIP(h, hipMemsetAsync(L.count, 0, MGC_NCOUNT * (1 + MGC_NSHARD) * sizeof(int32_t), h->stream));
+    h->zero_mask = 0;
+    h->pending_zero = -1;
+    h->filt[0] = h->filt[1] = 0;
+    if (L.ndir == 6) hipLaunchKernelGGL(k_update_tlinks<false>, dim3(grid), dim3(MGC_TV), 0, h->stream, L, A);
+    else hipLaunchKernelGGL(k_update_tlinks<true>, dim3(grid), dim3(MGC_TV), 0, h->stream, L, A);
+    MGC_HIP(h, hipGetLastError());
+    mgc_sum_partials(h, (int64_t)L.ntiles, h->d_scalar);
+    MGC_HIP(h, hipGetLastError());
+    MGC_HIP(h, hipEventRecord(h->ev[1], h->stream));
+    MGC_HIP(h, hipMemcpyAsync(h->h_scalar, h->d_scalar, 8 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    MGC_HIP(h, hipMemcpyAsync(h->h_count, L.count, MGC_NCOUNT * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    MGC_HIP(h, hipStreamSynchronize(h->stream));
+    if (L.ndir == 6) h->sink_tiles = h->h_count[MGC_CNT_SINK_TILES];
+    h->zero_mask |= 1u << MGC_CNT_SINK_TILES;
+    float ms = 0.f;
+    MGC_HIP(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+    h->stats.update_ms = ms;
+    h->flow_const = h->h_scalar[0] + (h->d_tr_in ? h->flow_const_in : 0.0); /* (bit for bit what mgc_build computes from these inputs) */
+    h->all_residual = false; /* saturated n-links: the first global relabel of the next solve runs as passes from scratch */
+    h->solved = false;
+    h->labels_valid = false;
+    h->labels_on_host = false;
+    h->op_spans.clear();
+    return MGC_OK;
+}
+
+int mgc_update_markers(mgc_handle h, const uint8_t* fg, const uint8_t* bg)
+{
+    if (!h) return MGC_ERR_INVALID;
+    { const int rc = mgc_update_check(h, "mgc_update_markers"); if (rc) return rc; }
+    MGC_HIP(h, hipSetDevice(h->device));
+    int rc = MGC_OK;
+    if (fg) rc = mgc_upload(h, (void**)&h->d_fg, fg, (size_t)h->nvox);
+    else if (h->d_fg) { (void)mgc_dfree(h->d_fg); h->d_fg = nullptr; }
+    if (rc) return rc;
+    if (bg) rc = mgc_upload(h, (void**)&h->d_bg, bg, (size_t)h->nvox);
+    else if (h->d_bg) { (void)mgc_dfree(h->d_bg); h->d_bg = nullptr; }
+    if (rc) return rc;
+    return mgc_update_tlinks(h);
+}
+
+int mgc_update_regional_probability(mgc_handle h, const void* pm, int dtype, double alpha)
+{
+    if (!h) return MGC_ERR_INVALID;
+    { const int rc = mgc_update_check(h, "mgc_update_regional_probability"); if (rc) return rc; }
+    if (!pm || (dtype != MGC_F32 && dtype != MGC_F64)) return mgc_fail(h, MGC_ERR_INVALID, "probability map must be float32 or float64");
+    MGC_HIP(h, hipSetDevice(h->device));
+    if (h->d_prob && h->prob_dtype != dtype) { (void)mgc_dfree(h->d_prob); h->d_prob = nullptr; }
+    h->prob_dtype = dtype;
+    h->alpha = alpha;
+    const int rc = mgc_upload(h, &h->d_prob, pm, (size_t)h->nvox * mgc_dtype_size(dtype));
+    if (rc) return rc;
+    return mgc_update_tlinks(h);
+}
+
 int mgc_validate(mgc_handle h, mgc_validation* out)
 {
     if (!h || !out) return MGC_ERR_INVALID;
@@ -4324,6 +4498,8 @@ int mgc_build(mgc_handle h)
     h->edges_applied = h->n_edges != 0;
     h->built = true;
     h->solved = false;
+    h->unconverged = false;
+    h->stats.update_ms = 0.0;
     h->labels_valid = false;
     h->op_spans.clear(); /* (launch-by-launch timing: the pairs of the solve before) */
     h->labels_on_host = false;
@@ -4391,6 +4567,7 @@ int mgc_maxflow(mgc_handle h, double* flow)
             h->stats.discharge_launches = dev.discharge_launches; h->stats.relabel_launches = dev.relabel_launches;
             h->stats.discharge_tiles = st.discharge_tiles; h->stats.relabel_tiles = st.relabel_tiles;
             h->stats.global_relabels = st.outer; h->stats.phases = st.phases;
+            h->unconverged = true;
             return mgc_fail(h, MGC_ERR_NOT_CONVERGED, "solver did not converge within %d global relabels", h->params.max_outer);
         }
         /* read-out: labels, then the capacity of the cut they define */

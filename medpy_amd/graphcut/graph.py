@@ -96,6 +96,13 @@ class VoxelGraph(object):
     (bin/medpy_graphcut_voxel.py:172-181, tests/graphcut_/energy_voxel.py:205-224):
     ``maxflow()``, ``what_segment(i)``, ``termtype``, ``get_edge``, ``get_node_num``,
     ``get_trcap`` -- plus bulk ``labels()`` so that nobody has to loop over voxels in Python.
+
+    Interactive re-segmentation (extension, in the spirit of the reference's ``set_trcap`` + ``maxflow()`` again):
+    ``update_markers(fg_markers, bg_markers)`` and ``update_regional_term(probability_map, alpha)`` replace the markers /
+    the regional term of the graph in place.  The n-links stay in HBM as they are, the residual graph of the last cut is
+    kept, and the next ``maxflow()`` continues from it (warm solve).  ``maxflow()``, ``labels()`` and
+    ``what_segment()`` then describe the cut of the new inputs -- the same labels and the same flow, bit for bit, as
+    ``graph_from_voxels`` of those inputs.  Explicit edges and t-weights that plug-in terms set stay part of the graph.
     """
 
     termtype = termtype
@@ -153,23 +160,51 @@ class VoxelGraph(object):
         if table is not None:
             self._call("mgc_set_boundary_lut", _lib.ptr(table), table.size)
 
-    def _set_regional(self, prob, alpha):
+    @staticmethod
+    def _prob_array(prob):
         prob = numpy.asarray(prob)
         if prob.dtype not in (numpy.float32, numpy.float64):
             prob = prob.astype(numpy.float64)  # NumPy promotes (non-float array * python float) to float64
-        prob = numpy.ascontiguousarray(prob)
+        return numpy.ascontiguousarray(prob)
+
+    def _set_regional(self, prob, alpha):
+        prob = self._prob_array(prob)
         self._call("mgc_set_regional_probability", _lib.ptr(prob), _lib.DTYPE_IDS[prob.dtype], float(alpha))
 
+    @staticmethod
+    def _marker_bytes(m):   # a C-contiguous bool array IS the byte array the library reads: no 1-byte-per-voxel copy (0.1 s at 512^3)
+        if m is None:
+            return None
+        m = numpy.asarray(m)
+        if m.dtype in (numpy.bool_, numpy.uint8, numpy.int8) and m.flags.c_contiguous:
+            return m.view(numpy.uint8)   # (the library reads "non-zero")
+        return numpy.ascontiguousarray(m, dtype=numpy.bool_).view(numpy.uint8)
+
     def _set_markers(self, fg, bg):
-        def as_bytes(m):   # a C-contiguous bool array IS the byte array the library reads: no 1-byte-per-voxel copy (0.1 s at 512^3)
-            if m is None:
-                return None
-            m = numpy.asarray(m)
-            if m.dtype in (numpy.bool_, numpy.uint8, numpy.int8) and m.flags.c_contiguous:
-                return m.view(numpy.uint8)   # (the library reads "non-zero")
-            return numpy.ascontiguousarray(m, dtype=numpy.bool_).view(numpy.uint8)
-        fg8, bg8 = as_bytes(fg), as_bytes(bg)
+        fg8, bg8 = self._marker_bytes(fg), self._marker_bytes(bg)
         self._call("mgc_set_markers", None if fg8 is None else _lib.ptr(fg8), None if bg8 is None else _lib.ptr(bg8))
+
+    def _check_volume_shape(self, a, what):
+        if a is not None and numpy.shape(a) != self._shape:
+            raise ValueError("%s of shape %s on a graph of shape %s" % (what, numpy.shape(a), self._shape))
+
+    # -- warm updates
+    def update_markers(self, fg_markers, bg_markers):
+        """Replace the foreground / background markers (arrays of the volume's shape, non-zero = marked; None = no markers of
+        that kind) and keep the residual graph: the next ``maxflow()`` is a warm solve of the graph with the new markers."""
+        self._check_volume_shape(fg_markers, "foreground markers")
+        self._check_volume_shape(bg_markers, "background markers")
+        fg8, bg8 = self._marker_bytes(fg_markers), self._marker_bytes(bg_markers)
+        self._labels = None
+        self._call("mgc_update_markers", None if fg8 is None else _lib.ptr(fg8), None if bg8 is None else _lib.ptr(bg8))
+
+    def update_regional_term(self, probability_map, alpha):
+        """Replace the regional term (foreground probability map of the volume's shape, weight ``alpha``; evaluated in the map's
+        dtype as ``regional_probability_map`` does) and keep the residual graph: the next ``maxflow()`` is a warm solve."""
+        self._check_volume_shape(probability_map, "probability map")
+        prob = self._prob_array(probability_map)
+        self._labels = None
+        self._call("mgc_update_regional_probability", _lib.ptr(prob), _lib.DTYPE_IDS[prob.dtype], float(alpha))
 
     def _add_edges(self, i, j, cap, rev):
         i = numpy.ascontiguousarray(i, dtype=numpy.int64)
@@ -318,6 +353,16 @@ class SparseGraph(object):
         self._raw_pairs = set()
         self._host_arcs = {}   # GraphFloat / GraphInt: (i, j) -> [capacity of the front arc, sum of the parallel arcs behind it]
         self._host_sent = {}   # ... (i, j) with i < j -> (capacity, reverse capacity) the device holds for the pair so far
+
+    def update_markers(self, fg_markers, bg_markers):
+        """Warm updates exist for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
+        raise NotImplementedError("medpy_amd: update_markers is implemented for the voxel lattice solver (1-D..3-D volumes, "
+                                  "VoxelGraph) only; this graph went to the sparse-graph solver: build it again from the new inputs")
+
+    def update_regional_term(self, probability_map, alpha):
+        """Warm updates exist for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
+        raise NotImplementedError("medpy_amd: update_regional_term is implemented for the voxel lattice solver (1-D..3-D volumes, "
+                                  "VoxelGraph) only; this graph went to the sparse-graph solver: build it again from the new inputs")
 
     def reset(self):
         """Graph::reset, reference graph.cpp:46-60 (wrapper.cpp:68): back to the state just after construction -- no nodes
@@ -670,6 +715,14 @@ class EmbeddedLatticeGraph(object):
 
     def get_edge(self, i, j):
         return self._inner.get_edge(i, j) if (i < self._n and j < self._n) else 0.0
+
+    def update_markers(self, fg_markers, bg_markers):
+        raise NotImplementedError("medpy_amd: update_markers is not implemented for a graph whose boundary image has another shape "
+                                  "than its markers (EmbeddedLatticeGraph): build it again with graph_from_voxels")
+
+    def update_regional_term(self, probability_map, alpha):
+        raise NotImplementedError("medpy_amd: update_regional_term is not implemented for a graph whose boundary image has another "
+                                  "shape than its markers (EmbeddedLatticeGraph): build it again with graph_from_voxels")
 
     def stats(self):
         return self._inner.stats()
