@@ -214,6 +214,21 @@ int mgc_get_stats(mgc_handle h, mgc_stats* out);
 /* development aid (mgc_set_param "profile_sections" 1): out16[0..3] = shader cycles of workgroup lane 0 spent in
  * load+absorb / in-tile labels / push sweeps / store of k_discharge, out16[8..11] = how many such sections */
 int mgc_get_profile(mgc_handle h, uint64_t* out16);
+/* Which form of the solver kernels the last solve of the handle ran (mgc_maxflow, or the slab's part of mgc_solve_slabs): out[k] = launches
+ * of kind k for k < min(n, MGC_NLAUNCH).  The parameters wave_kernels / use_filters / wave_min_tiles pick the form; the grid parameters
+ * (grid26_dis, wave_grid_dis, wave_grid_rel, wave_grid26) size one form each, so a test of a grid can check that its kernel ran. */
+enum {
+    MGC_LAUNCH_DISCHARGE = 0,     /* k_discharge: one workgroup per tile (6-neighbourhood)                 */
+    MGC_LAUNCH_DISCHARGE_W = 1,   /* k_discharge_w: one wave per tile, persistent grid wave_grid_dis      */
+    MGC_LAUNCH_RELABEL_TILE = 2,  /* k_relabel_all / k_relabel_first_list / k_relabel_list / k_relabel_b  */
+    MGC_LAUNCH_RELABEL_V = 3,     /* k_relabel_v                                                           */
+    MGC_LAUNCH_RELABEL_W = 4,     /* k_relabel_w: one wave per tile, persistent grid wave_grid_rel        */
+    MGC_LAUNCH_DISCHARGE26 = 5,   /* k26_discharge: grid grid26_dis (0: grid_cap)                         */
+    MGC_LAUNCH_DISCHARGE26_V = 6, /* k26_discharge_v                                                       */
+    MGC_LAUNCH_DISCHARGE26_W = 7, /* k26_discharge_w: one wave per tile, persistent grid wave_grid26      */
+    MGC_NLAUNCH = 8
+};
+int mgc_get_launch_counts(mgc_handle h, int64_t* out, int n);
 
 /* ------------------------------------------------------------------------------------------
  * Z-slab decomposition across the GPUs of one node (no reference counterpart: the reference is

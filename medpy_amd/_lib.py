@@ -43,6 +43,10 @@ class Stats(C.Structure):
         return d
 
 
+# mgc_get_launch_counts: the kinds of solver launch, in the order of MGC_LAUNCH_* (include/medpy_hip.h)
+LAUNCH_KINDS = ("k_discharge", "k_discharge_w", "k_relabel_tile", "k_relabel_v", "k_relabel_w", "k26_discharge", "k26_discharge_v", "k26_discharge_w")
+
+
 class Validation(C.Structure):
     """mgc_validation (include/medpy_hip.h): invariants of a maximum preflow, counted on the device"""
     _fields_ = [("voxels", C.c_int64), ("negative_values", C.c_int64), ("active_excess", C.c_int64),
@@ -141,6 +145,7 @@ SIGNATURES = {
     "mgc_set_image_range": (_INT, [_VP, _VP]),
     "mgc_get_stats": (_INT, [_VP, C.POINTER(Stats)]),
     "mgc_get_profile": (_INT, [_VP, _VP]),
+    "mgc_get_launch_counts": (_INT, [_VP, _VP, _INT]),
     # Z-slab decomposition (multi-GPU)
     "mgc_create_slab": (_INT, [_INT, C.POINTER(_I64), _INT, _INT, _INT, _INT, C.POINTER(_VP)]),
     "mgc_slab_info": (_INT, [_VP, C.POINTER(_I64)]),

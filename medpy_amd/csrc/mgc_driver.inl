@@ -305,7 +305,11 @@ int mgc_solve(Dev& dev, const MgcLattice& L, const MgcSolveParams& P, MgcSolveSt
         /* Z-slabs: border labels + outbox flow cross once per ROUND of the two colours (6-neighbourhood; every `exchange_rounds` rounds):
          * what a tile pushed over the slab border waits in its outbox until then -- region discharge only ever assumes a neighbour's
          * labels and outbox as of SOME earlier moment -- and mgc_halo_unpack_tile queues the receiving tile for the next phase of ITS
-         * colour.  The full neighbourhood pushes into the ghost tiles in place and exchanges after every phase. */
+         * colour.  The full neighbourhood pushes into the ghost tiles in place and exchanges after every phase.
+         * Invariant: the rounds never end with border outbox flow undelivered.  Flow in an outbox that faces a ghost tile is invisible
+         * to the counters read below (they count queued tiles and what a full message deferred), so a round that may end the cycle --
+         * the last one, and every `check_rounds`-th, where a break on `stop_below` can fall -- always exchanges.  (Counting the border
+         * outboxes instead would cost a pass over them at every look; with the defaults, 8 a multiple of 2, no exchange is added.) */
         const bool multi = dev.multi();
         const int xr = P.exchange_rounds > 0 ? P.exchange_rounds : 1;
         if (multi) dev.zero_count(MGC_CNT_DEFERRED);
@@ -314,7 +318,7 @@ int mgc_solve(Dev& dev, const MgcLattice& L, const MgcSolveParams& P, MgcSolveSt
                 const int lst = (int)(phase & (uint32_t)lay.list_mask);
                 dev.discharge(lst, phase, P.max_cycles, P.max_sweeps);
                 dev.zero_count(lst);
-                if (multi && (lay.ncolours != 2 || (c == 1 && ((r + 1) % xr == 0 || r + 1 == rounds_now)))) dev.exchange(1, phase, 0);
+                if (multi && (lay.ncolours != 2 || (c == 1 && ((r + 1) % xr == 0 || (r + 1) % P.check_rounds == 0 || r + 1 == rounds_now)))) dev.exchange(1, phase, 0);
                 st.phases++;
                 phase++;
             }

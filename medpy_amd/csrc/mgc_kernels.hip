@@ -2664,6 +2664,7 @@ struct mgc_graph {
     int w26_passes = 2, w26_raises = 1, w26_flags = 0; /* k26_discharge_w: passes over the steps / relabel rounds per sweep, MGCW26_* flags */
     int activate_exact_max = 4096; /* activation looks at the voxels of its candidate tiles only when there are at most this many (mgcw_activate_tile) */
     int wave_stagger = 0;          /* development knob of k_discharge_w (see there) */
+    int64_t launches[MGC_NLAUNCH] = {}; /* solver launches of the last solve by kernel form (mgc_get_launch_counts) */
     /* k_discharge_w<MGCW_REPEAT_MAX> (in-plane push steps repeated within a sweep, mgc_wave_ops.inl) -- parameter repeat_steps: bit 0 = for
      * graphs solved on exact labels throughout (no walls: weak contrast, integer-valued images, markers everywhere), bit 1 = also for graphs
      * whose flood runs on radial labels.  Measured on MI355X (profiles/r6_ab_repeat_policy.jsonl): 512^3 ct 73.4 -> 52.1 ms, hard 63.4 -> 59.7,
@@ -2914,13 +2915,13 @@ struct HipDevT {
         h->brick_mode = false; /* a from-scratch relabel runs over tiles */
         const int id = time_begin(1);
         if constexpr (FULL) hipLaunchKernelGGL(k26_relabel_all, dim3(grid(h->L.ntiles)), dim3(MGC_TV), 0, h->stream, h->L, epoch, next);
-        else if (!(h->use_filters & 1)) hipLaunchKernelGGL(k_relabel_all, dim3(grid(h->L.ntiles)), dim3(MGC_TV), 0, h->stream, h->L, epoch, next);
+        else if (!(h->use_filters & 1)) { hipLaunchKernelGGL(k_relabel_all, dim3(grid(h->L.ntiles)), dim3(MGC_TV), 0, h->stream, h->L, epoch, next); h->launches[MGC_LAUNCH_RELABEL_TILE]++; }
         else { /* one thread per tile finds the seeds (tiles with an arc to the sink); only those get a workgroup */
             flush_zero();
             hipLaunchKernelGGL(k_filter, dim3(filter_grid()), dim3(256), 0, h->stream, h->L, 3, 6, fslot(0));
-            if (h->wave_kernels & 8) { hipLaunchKernelGGL(k_relabel_v, dim3(grid(h->L.ntiles)), dim3(MGC_TV / MGC_RELABEL_V), 0, h->stream, h->L, 6, fslot(0), epoch, next, fnext(0), 1); filter_done(0, true); }
-            else if (h->wave_kernels & 2) { hipLaunchKernelGGL(k_relabel_w, dim3(h->wave_grid_rel), dim3(MGCW_LANES), 0, h->stream, h->L, 6, fslot(0), epoch, next, -1, 1, h->tk_rel); h->tk_rel ^= 1; filter_done(0, false); }
-            else { hipLaunchKernelGGL(k_relabel_first_list, dim3(grid(h->L.ntiles)), dim3(MGC_TV), 0, h->stream, h->L, 6, fslot(0), epoch, next); filter_done(0, false); }
+            if (h->wave_kernels & 8) { hipLaunchKernelGGL(k_relabel_v, dim3(grid(h->L.ntiles)), dim3(MGC_TV / MGC_RELABEL_V), 0, h->stream, h->L, 6, fslot(0), epoch, next, fnext(0), 1); filter_done(0, true); h->launches[MGC_LAUNCH_RELABEL_V]++; }
+            else if (h->wave_kernels & 2) { hipLaunchKernelGGL(k_relabel_w, dim3(h->wave_grid_rel), dim3(MGCW_LANES), 0, h->stream, h->L, 6, fslot(0), epoch, next, -1, 1, h->tk_rel); h->tk_rel ^= 1; filter_done(0, false); h->launches[MGC_LAUNCH_RELABEL_W]++; }
+            else { hipLaunchKernelGGL(k_relabel_first_list, dim3(grid(h->L.ntiles)), dim3(MGC_TV), 0, h->stream, h->L, 6, fslot(0), epoch, next); filter_done(0, false); h->launches[MGC_LAUNCH_RELABEL_TILE]++; }
         }
         check(hipGetLastError());
         time_end(id);
@@ -3022,11 +3023,11 @@ struct HipDevT {
     {
         flush_zero();
         const int id = time_begin(1);
-        if (!FULL && h->brick_mode) hipLaunchKernelGGL(k_relabel_b, dim3(grid(mgc_brick_count(h->L))), dim3(MGC_TV), 0, h->stream, h->L, lst, epoch, next, zero_list);
+        if (!FULL && h->brick_mode) { hipLaunchKernelGGL(k_relabel_b, dim3(grid(mgc_brick_count(h->L))), dim3(MGC_TV), 0, h->stream, h->L, lst, epoch, next, zero_list); h->launches[MGC_LAUNCH_RELABEL_TILE]++; }
         else if constexpr (FULL) hipLaunchKernelGGL(k26_relabel_list, dim3(grid(h->L.ntiles)), dim3(MGC_TV), 0, h->stream, h->L, lst, epoch, next);
-        else if (h->wave_kernels & 8) hipLaunchKernelGGL(k_relabel_v, dim3(grid(h->L.ntiles)), dim3(MGC_TV / MGC_RELABEL_V), 0, h->stream, h->L, lst, lst, epoch, next, zero_list, 0);
-        else if (h->wave_kernels & 2) { hipLaunchKernelGGL(k_relabel_w, dim3(h->wave_grid_rel), dim3(MGCW_LANES), 0, h->stream, h->L, lst, lst, epoch, next, zero_list, 0, h->tk_rel); h->tk_rel ^= 1; }
-        else hipLaunchKernelGGL(k_relabel_list, dim3(grid(h->L.ntiles)), dim3(MGC_TV), 0, h->stream, h->L, lst, epoch, next, zero_list);
+        else if (h->wave_kernels & 8) { hipLaunchKernelGGL(k_relabel_v, dim3(grid(h->L.ntiles)), dim3(MGC_TV / MGC_RELABEL_V), 0, h->stream, h->L, lst, lst, epoch, next, zero_list, 0); h->launches[MGC_LAUNCH_RELABEL_V]++; }
+        else if (h->wave_kernels & 2) { hipLaunchKernelGGL(k_relabel_w, dim3(h->wave_grid_rel), dim3(MGCW_LANES), 0, h->stream, h->L, lst, lst, epoch, next, zero_list, 0, h->tk_rel); h->tk_rel ^= 1; h->launches[MGC_LAUNCH_RELABEL_W]++; }
+        else { hipLaunchKernelGGL(k_relabel_list, dim3(grid(h->L.ntiles)), dim3(MGC_TV), 0, h->stream, h->L, lst, epoch, next, zero_list); h->launches[MGC_LAUNCH_RELABEL_TILE]++; }
         check(hipGetLastError());
         time_end(id);
         relabel_launches++;
@@ -3088,9 +3089,10 @@ struct HipDevT {
             if (((h->wave_kernels & 32) || h->w26_auto) && cycles < 0) { /* one wave per tile, the tile in registers (stored labels only) */
                 hipLaunchKernelGGL(k26_discharge_w, dim3(h->wave_grid26), dim3(MGCW_LANES), 0, h->stream, h->L, lst, phase, sweeps, h->w26_auto ? 1 : h->w26_passes, h->w26_raises, h->w26_flags, h->tk_dis, zero_idx);
                 h->tk_dis ^= 1;
+                h->launches[MGC_LAUNCH_DISCHARGE26_W]++;
             }
-            else if (h->wave_kernels & 16) hipLaunchKernelGGL(k26_discharge_v, dim3(grid(h->L.ntiles)), dim3(MGC_TV / 2), 0, h->stream, h->L, lst, phase, cycles, sweeps, zero_idx);
-            else hipLaunchKernelGGL(k26_discharge, dim3(h->grid26_dis > 0 ? (h->grid26_dis < h->L.ntiles ? h->grid26_dis : h->L.ntiles) : grid(h->L.ntiles)), dim3(MGC_TV), 0, h->stream, h->L, lst, phase, cycles, sweeps, zero_idx);
+            else if (h->wave_kernels & 16) { hipLaunchKernelGGL(k26_discharge_v, dim3(grid(h->L.ntiles)), dim3(MGC_TV / 2), 0, h->stream, h->L, lst, phase, cycles, sweeps, zero_idx); h->launches[MGC_LAUNCH_DISCHARGE26_V]++; }
+            else { hipLaunchKernelGGL(k26_discharge, dim3(h->grid26_dis > 0 ? (h->grid26_dis < h->L.ntiles ? h->grid26_dis : h->L.ntiles) : grid(h->L.ntiles)), dim3(MGC_TV), 0, h->stream, h->L, lst, phase, cycles, sweeps, zero_idx); h->launches[MGC_LAUNCH_DISCHARGE26]++; }
         }
         /* one wave per tile has the higher throughput (2 048 tiles in flight, fewer instructions per tile), eight waves per tile
          * the shorter latency (36 us against 60 us for one tile): short lists -- small volumes, the tail of a solve -- are a
@@ -3106,9 +3108,13 @@ struct HipDevT {
             if (rep) hipLaunchKernelGGL(k_discharge_w<MGCW_REPEAT_MAX>, dim3(h->wave_grid_dis), dim3(MGCW_LANES), 0, h->stream, h->L, lst, phase, sweeps, dflags, h->tk_dis, zero_idx, h->wave_stagger);
             else hipLaunchKernelGGL(k_discharge_w<1>, dim3(h->wave_grid_dis), dim3(MGCW_LANES), 0, h->stream, h->L, lst, phase, sweeps, dflags, h->tk_dis, zero_idx, h->wave_stagger);
             h->tk_dis ^= 1;
+            h->launches[MGC_LAUNCH_DISCHARGE_W]++;
         }
-        else hipLaunchKernelGGL(k_discharge, dim3(grid(h->L.ntiles)), dim3(MGC_TV), 0, h->stream, h->L, lst, phase,
-                                (h->wave_kernels & 1) && !(h->wave_kernels & 4) ? (h->radial_on ? (h->radial_cycle_no > 1 ? -3 : -2) : -1) : cycles, sweeps, zero_idx); /* same labelling policy as the wave form (-2: radial labels, any saturation marks the tile) */
+        else {
+            hipLaunchKernelGGL(k_discharge, dim3(grid(h->L.ntiles)), dim3(MGC_TV), 0, h->stream, h->L, lst, phase,
+                               (h->wave_kernels & 1) && !(h->wave_kernels & 4) ? (h->radial_on ? (h->radial_cycle_no > 1 ? -3 : -2) : -1) : cycles, sweeps, zero_idx); /* same labelling policy as the wave form (-2: radial labels, any saturation marks the tile) */
+            h->launches[MGC_LAUNCH_DISCHARGE]++;
+        }
         check(hipGetLastError());
         time_end(id);
         discharge_launches++;
@@ -3930,6 +3936,7 @@ static int mgc_solve_slabs_on(mgc_handle* hs, int n, const mgc_transport* cb, co
          * and a slab's kernels run alone on the device (what is measured per slab is what a device of its own would take) */
         own_stream[(size_t)i] = hs[i]->stream;
         hs[i]->stream = h0->stream;
+        for (int64_t& k : hs[i]->launches) k = 0;
         hs[i]->timing_offset++;
         hs[i]->solved = false;
     }
@@ -4516,6 +4523,7 @@ int mgc_maxflow(mgc_handle h, double* flow)
     if (!h->solved) {
         MgcRange range_("mgc_maxflow");
         MgcSolveStats st;
+        for (int64_t& n : h->launches) n = 0;
         MGC_HIP(h, hipEventRecord(h->ev[0], h->stream));
         HipDev dev;
         HipDev26 dev26;
@@ -4772,8 +4780,8 @@ int mgc_set_param(mgc_handle h, const char* name, int64_t value)
     else if (!strcmp(name, "radial_budget_x16") && value >= 1) h->params.radial_budget_x16 = (int)value;
     else if (!strcmp(name, "radial_min_c") && value >= 1) h->params.radial_min_c = (int)value;
     else if (!strcmp(name, "radial_rounds0") && value >= 0) h->params.radial_rounds0 = (int)value; /* 0: one radial cycle of the whole budget */
-    else if (!strcmp(name, "use_filters")) h->use_filters = (int)value;
-    else if (!strcmp(name, "wave_kernels")) { h->wave_kernels = (int)value; h->wave_set = true; }
+    else if (!strcmp(name, "use_filters") && value >= 0 && value <= 7) h->use_filters = (int)value;       /* bits 0 - 2: absorb, activate, reset-suspect */
+    else if (!strcmp(name, "wave_kernels") && value >= 0 && value <= 63) { h->wave_kernels = (int)value; h->wave_set = true; } /* bits 0 - 5 */
     else if (!strcmp(name, "wave_min_tiles") && value >= 0) h->wave_min_tiles = (int)value;
     else if (!strcmp(name, "sweeps_sparse26") && value >= 0) { h->sweeps_sparse26 = (int)value; h->sparse26_set = true; }
     else if (!strcmp(name, "wave_grid_dis") && value > 0) h->wave_grid_dis = (int)value;
@@ -4825,6 +4833,13 @@ int mgc_get_profile(mgc_handle h, uint64_t* out16)
     if (!h->L.prof) return MGC_OK;
     MGC_HIP(h, hipSetDevice(h->device));
     MGC_HIP(h, hipMemcpy(out16, h->L.prof, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return MGC_OK;
+}
+
+int mgc_get_launch_counts(mgc_handle h, int64_t* out, int n)
+{
+    if (!h || !out || n < 0) return MGC_ERR_INVALID;
+    for (int k = 0; k < n && k < MGC_NLAUNCH; ++k) out[k] = h->launches[k];
     return MGC_OK;
 }
 

@@ -296,6 +296,12 @@ class VoxelGraph(object):
         self._call("mgc_get_stats", C.byref(st))
         return st.as_dict()
 
+    def launch_counts(self):
+        """{kernel form: launches} of the last solve (mgc_get_launch_counts; names: _lib.LAUNCH_KINDS)"""
+        out = numpy.zeros(len(_lib.LAUNCH_KINDS), dtype=numpy.int64)
+        self._call("mgc_get_launch_counts", _lib.ptr(out), int(out.size))
+        return dict(zip(_lib.LAUNCH_KINDS, out.tolist()))
+
 
 class SparseGraph(object):
     """``maxflow.GraphDouble`` (reference lib/maxflow/src/wrapper.cpp:59-89) for ARBITRARY graphs, solved in HBM by the

@@ -134,7 +134,8 @@ def sync_boundary_table(slabs, ex):
 
 
 def solve_slabs(slabs, ex=None, rounds_per_relabel=None, max_cycles=None, max_sweeps=None, max_outer=None, check_rounds=None, relabel_batch=None,
-                incremental_relabel=True, exchange_every=None, exchange_rounds=None, radial=None):
+                incremental_relabel=True, exchange_every=None, exchange_rounds=None, radial=None, stop_below=None, adaptive_rounds=None,
+                radial_min_c=None, radial_rounds0=None, radial_budget_x16=None, trace=None):
     """Drives the local slabs to a maximum preflow.  Returns a stats dict (global numbers).
 
     There is ONE schedule, and it is not here: ``mgc_solve`` (medpy_amd/csrc/mgc_driver.inl) -- the single handle's own, with the
@@ -149,10 +150,14 @@ def solve_slabs(slabs, ex=None, rounds_per_relabel=None, max_cycles=None, max_sw
     * one slab and a host transport (``StoreExchange``; the gloo transport of the tests): borders through the transport's
       ``xchg`` / ``allreduce_i64`` / ``send`` / ``recv``, handed to the library as the callbacks of an ``mgc_transport``.
 
-    ``None`` leaves a parameter at the library's default for the slab's neighbourhood."""
+    The keywords are the schedule knobs of ``MgcSolveParams`` (``exchange_every`` is ``exchange_passes``), handed on by name to either
+    kind of slab; a name that is not one of them is refused (TypeError), and so is a value the slab refuses.  ``None`` leaves a parameter
+    at the library's default for the slab's neighbourhood."""
     params = {"rounds_per_relabel": rounds_per_relabel, "max_cycles": max_cycles, "max_sweeps": max_sweeps, "max_outer": max_outer,
               "check_rounds": check_rounds, "relabel_batch": relabel_batch, "incremental_relabel": int(bool(incremental_relabel)),
-              "exchange_passes": exchange_every, "exchange_rounds": exchange_rounds, "radial": radial}
+              "exchange_passes": exchange_every, "exchange_rounds": exchange_rounds, "radial": radial, "stop_below": stop_below,
+              "adaptive_rounds": adaptive_rounds, "radial_min_c": radial_min_c, "radial_rounds0": radial_rounds0,
+              "radial_budget_x16": radial_budget_x16, "trace": None if trace is None else int(bool(trace))}
     transport = None
     if len(slabs) == 1 and ex is not None and not getattr(ex, "native", False) and not isinstance(ex, LoopbackExchange):
         transport = ex

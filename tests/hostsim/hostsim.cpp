@@ -843,32 +843,98 @@ int hostsim_halo_unpack(void* h, int side, int kind, const void* buf, int on_dev
 int hostsim_labels(void* h, uint8_t* out) { ((HostDev*)h)->labels(out); return 0; }
 void hostsim_set_halo_max(void* h, int which, int n);
 
-/* ---- one-call convenience: single slab, the C++ schedule of mgc_driver.inl ---- */
-int hostsim_solve(const int64_t* shape, const double* w0, const double* w1, const double* w2, const double* trcap,
-                  int rounds, int cycles, int sweeps, int max_outer, uint8_t* labels_out, int64_t* stats_out)
+/* ---- every schedule knob of MgcSolveParams as one parameter vector (tests/hostsim/sim.py: SCHEDULE_KNOBS, same order) ----
+ * An entry of HOSTSIM_KEEP leaves the default of the neighbourhood; any other value is one that mgc_set_param accepts for that knob
+ * (the ranges below are its).  Returns 0, or 1 + the index of the first entry it refuses (P is then incomplete). */
+enum { HP_ROUNDS, HP_CYCLES, HP_SWEEPS, HP_OUTER, HP_INCREMENTAL, HP_XPASSES, HP_RADIAL, HP_XROUNDS, HP_CHECK_ROUNDS, HP_RELABEL_BATCH,
+       HP_STOP_BELOW, HP_ADAPTIVE, HP_RADIAL_MIN_C, HP_RADIAL_ROUNDS0, HP_RADIAL_BUDGET, HP_TRACE, HP_NPARAM };
+static const int64_t HOSTSIM_KEEP = INT64_MIN;
+
+static int hostsim_params(const int64_t* v, int n, MgcSolveParams& P)
 {
-    const int incremental = max_outer >= 0;
-    if (max_outer < 0) max_outer = -max_outer - 1; /* negative: from-scratch relabels only (A/B tests) */
-    HostDev* d = (HostDev*)hostsim_create(shape, 0, 1);
-    d->load(w0, w1, w2, trcap);
-    MgcSolveParams P = mgc_default_params();
-    if (rounds > 0) P.rounds_per_relabel = rounds;
-    if (cycles > 0) P.max_cycles = cycles;
-    if (sweeps > 0) P.max_sweeps = sweeps;
-    if (max_outer > 0) P.max_outer = max_outer;
-    P.incremental_relabel = incremental;
+    if (n > HP_NPARAM) return 1 + HP_NPARAM;
+    for (int i = 0; i < n; ++i) {
+        const int64_t x = v[i];
+        if (x == HOSTSIM_KEEP) continue;
+        if (x < -0x7fffffffLL || x > 0x7fffffffLL) return 1 + i;
+        const int k = (int)x;
+        bool ok = k > 0;
+        switch (i) {
+        case HP_ROUNDS: P.rounds_per_relabel = k; break;
+        case HP_CYCLES: ok = k != 0; P.max_cycles = k; break; /* < 0: the stored labels instead of an exact in-tile labelling */
+        case HP_SWEEPS: P.max_sweeps = k; break;
+        case HP_OUTER: P.max_outer = k; break;
+        case HP_INCREMENTAL: ok = true; P.incremental_relabel = k != 0; break;
+        case HP_XPASSES: P.exchange_passes = k; break;
+        case HP_RADIAL: ok = k >= 0 && k <= 2; P.radial = k; break;
+        case HP_XROUNDS: P.exchange_rounds = k; break;
+        case HP_CHECK_ROUNDS: P.check_rounds = k; break;
+        case HP_RELABEL_BATCH: P.relabel_batch = k; break;
+        case HP_STOP_BELOW: ok = k >= 0; P.stop_below = k; break;
+        case HP_ADAPTIVE: ok = k >= 0; P.adaptive_rounds = k; break;
+        case HP_RADIAL_MIN_C: P.radial_min_c = k; break;
+        case HP_RADIAL_ROUNDS0: ok = k >= 0; P.radial_rounds0 = k; break;
+        case HP_RADIAL_BUDGET: P.radial_budget_x16 = k; break;
+        case HP_TRACE: ok = true; P.trace = k != 0; break;
+        }
+        if (!ok) return 1 + i;
+    }
+    return 0;
+}
+
+/* how many entries hostsim_params takes (tests/hostsim/sim.py checks SCHEDULE_KNOBS against it) */
+int hostsim_param_count() { return HP_NPARAM; }
+
+/* the environment variables of the development tools (tools/sim_workprofile.py and kin) */
+static void hostsim_env_params(MgcSolveParams& P, int ndir)
+{
     if (getenv("HOSTSIM_TRACE")) P.trace = atoi(getenv("HOSTSIM_TRACE")); /* one stderr line per global relabel (tools/sim_workprofile.py) */
-    if (getenv("HOSTSIM_ADAPTIVE")) P.adaptive_rounds = atoi(getenv("HOSTSIM_ADAPTIVE"));
     if (getenv("HOSTSIM_RADIAL")) P.radial = atoi(getenv("HOSTSIM_RADIAL"));
+    if (getenv("HOSTSIM_RADIAL_BUDGET")) P.radial_budget_x16 = atoi(getenv("HOSTSIM_RADIAL_BUDGET"));
+    if (ndir == 26) return;
+    if (getenv("HOSTSIM_ADAPTIVE")) P.adaptive_rounds = atoi(getenv("HOSTSIM_ADAPTIVE"));
     if (getenv("HOSTSIM_RADIAL_ROUNDS0")) P.radial_rounds0 = atoi(getenv("HOSTSIM_RADIAL_ROUNDS0"));
     if (getenv("HOSTSIM_RADIAL_MIN_C")) P.radial_min_c = atoi(getenv("HOSTSIM_RADIAL_MIN_C"));
-    if (getenv("HOSTSIM_RADIAL_BUDGET")) P.radial_budget_x16 = atoi(getenv("HOSTSIM_RADIAL_BUDGET"));
+}
+
+static int hostsim_solve_with(const int64_t* shape, const double* w0, const double* w1, const double* w2, const double* trcap,
+                              const MgcSolveParams& P, uint8_t* labels_out, int64_t* stats_out)
+{
+    HostDev* d = (HostDev*)hostsim_create(shape, 0, 1);
+    d->load(w0, w1, w2, trcap);
     MgcSolveStats st;
     const int rc = mgc_solve(*d, d->L, P, st);
     memcpy(stats_out, &st, sizeof(st));
     d->labels(labels_out);
     delete d;
     return rc;
+}
+
+/* ---- one-call convenience: single slab, the C++ schedule of mgc_driver.inl ---- */
+int hostsim_solve(const int64_t* shape, const double* w0, const double* w1, const double* w2, const double* trcap,
+                  int rounds, int cycles, int sweeps, int max_outer, uint8_t* labels_out, int64_t* stats_out)
+{
+    const int incremental = max_outer >= 0;
+    if (max_outer < 0) max_outer = -max_outer - 1; /* negative: from-scratch relabels only (A/B tests) */
+    MgcSolveParams P = mgc_default_params();
+    if (rounds > 0) P.rounds_per_relabel = rounds;
+    if (cycles > 0) P.max_cycles = cycles;
+    if (sweeps > 0) P.max_sweeps = sweeps;
+    if (max_outer > 0) P.max_outer = max_outer;
+    P.incremental_relabel = incremental;
+    hostsim_env_params(P, 6);
+    return hostsim_solve_with(shape, w0, w1, w2, trcap, P, labels_out, stats_out);
+}
+
+/* the same with every schedule knob (hostsim_params; the environment first, the vector over it); returns -(1 + index) for a refused entry */
+int hostsim_solve_p(const int64_t* shape, const double* w0, const double* w1, const double* w2, const double* trcap,
+                    const int64_t* params, int nparams, uint8_t* labels_out, int64_t* stats_out)
+{
+    MgcSolveParams P = mgc_default_params();
+    hostsim_env_params(P, 6);
+    const int bad = hostsim_params(params, nparams, P);
+    if (bad) return -bad;
+    return hostsim_solve_with(shape, w0, w1, w2, trcap, P, labels_out, stats_out);
 }
 
 /* the first global relabel of a solve alone (use_dt: as a distance transform when the graph allows it, else by relaxation
@@ -1144,20 +1210,35 @@ struct HostDev26 : HostSlabOps<HostDev26, HostBlockT<MgcTileShared26D>> {
 
 extern "C" {
 
+static int hostsim_solve26_with(const int64_t* shape, const double* w, const double* trcap, const MgcSolveParams& P, uint8_t* labels_out, int64_t* stats_out);
+
 int hostsim_solve26(const int64_t* shape, const double* w, const double* trcap, int rounds, int cycles, int sweeps, int max_outer,
                     uint8_t* labels_out, int64_t* stats_out)
 {
-    HostDev26* d = new HostDev26();
-    d->init(shape[0], shape[1], shape[2], NULL);
-    d->load(w, trcap);
     MgcSolveParams P = mgc_default_params(26);
     if (rounds > 0) P.rounds_per_relabel = rounds;
     if (cycles != 0) P.max_cycles = cycles; /* < 0: stored labels instead of the exact in-tile labelling */
     if (sweeps > 0) P.max_sweeps = sweeps;
     if (max_outer > 0) P.max_outer = max_outer;
-    if (getenv("HOSTSIM_RADIAL")) P.radial = atoi(getenv("HOSTSIM_RADIAL"));
-    if (getenv("HOSTSIM_RADIAL_BUDGET")) P.radial_budget_x16 = atoi(getenv("HOSTSIM_RADIAL_BUDGET"));
-    if (getenv("HOSTSIM_TRACE")) P.trace = atoi(getenv("HOSTSIM_TRACE"));
+    hostsim_env_params(P, 26);
+    return hostsim_solve26_with(shape, w, trcap, P, labels_out, stats_out);
+}
+
+/* every schedule knob (hostsim_params, as hostsim_solve_p) */
+int hostsim_solve26_p(const int64_t* shape, const double* w, const double* trcap, const int64_t* params, int nparams, uint8_t* labels_out, int64_t* stats_out)
+{
+    MgcSolveParams P = mgc_default_params(26);
+    hostsim_env_params(P, 26);
+    const int bad = hostsim_params(params, nparams, P);
+    if (bad) return -bad;
+    return hostsim_solve26_with(shape, w, trcap, P, labels_out, stats_out);
+}
+
+static int hostsim_solve26_with(const int64_t* shape, const double* w, const double* trcap, const MgcSolveParams& P, uint8_t* labels_out, int64_t* stats_out)
+{
+    HostDev26* d = new HostDev26();
+    d->init(shape[0], shape[1], shape[2], NULL);
+    d->load(w, trcap);
     MgcSolveStats st;
     const int rc = mgc_solve(*d, d->L, P, st, mgc_layout26());
     memcpy(stats_out, &st, sizeof(st));
@@ -1244,10 +1325,10 @@ int hostsim26_labels(void* h, uint8_t* out) { ((HostDev26*)h)->labels(out); retu
 
 /* The slabs of one volume through mgc_solve (mgc_driver.inl) -- the schedule the library runs for them (mgc_solve_slabs), with the same
  * group and transport code: n = all slabs of the volume (handles of this process), or n = 1 with the callbacks of a host transport.
- * params[0..7]: rounds_per_relabel, max_cycles, max_sweeps, max_outer, incremental_relabel, exchange_passes, radial (-1: the default), exchange_rounds
- * (0 / as noted: the default).  stats_out[0..15]: MgcSolveStats, then exchanges, reductions. */
+ * params[0..nparams): the schedule knobs in the order of hostsim_params (HOSTSIM_KEEP: the default).  stats_out[0..15]: MgcSolveStats,
+ * then exchanges, reductions.  Returns -(1 + index) for a refused entry. */
 template <class Dev>
-static int hostsim_solve_slabs_on(void** handles, int n, const mgc_transport* cb, const int64_t* params, const MgcLayout lay, int ndir, int64_t* stats_out)
+static int hostsim_solve_slabs_on(void** handles, int n, const mgc_transport* cb, const int64_t* params, int nparams, const MgcLayout lay, int ndir, int64_t* stats_out)
 {
     std::vector<Dev*> ptr((size_t)n);
     for (int i = 0; i < n; ++i) ptr[(size_t)i] = (Dev*)handles[i];
@@ -1255,16 +1336,10 @@ static int hostsim_solve_slabs_on(void** handles, int n, const mgc_transport* cb
     MgcXchg<Dev> x(ptr, cb, all_local);
     MgcSlabGroup<Dev, MgcXchg<Dev>> group(ptr, x);
     MgcSolveParams P = mgc_default_params(ndir);
-    if (params[0] > 0) P.rounds_per_relabel = (int)params[0];
-    if (params[1] != 0) P.max_cycles = (int)params[1];
-    if (params[2] > 0) P.max_sweeps = (int)params[2];
-    if (params[3] > 0) P.max_outer = (int)params[3];
-    P.incremental_relabel = params[4] != 0;
-    if (params[5] > 0) P.exchange_passes = (int)params[5];
-    if (params[6] >= 0) P.radial = (int)params[6];
-    if (params[7] > 0) P.exchange_rounds = (int)params[7];
     if (getenv("HOSTSIM_TRACE")) P.trace = atoi(getenv("HOSTSIM_TRACE"));
     if (getenv("HOSTSIM_RADIAL_MIN_C")) P.radial_min_c = atoi(getenv("HOSTSIM_RADIAL_MIN_C"));
+    const int bad = hostsim_params(params, nparams, P);
+    if (bad) return -bad;
     MgcSolveStats st;
     const int rc = mgc_solve(group, ptr[0]->L, P, st, lay);
     memset(stats_out, 0, 16 * sizeof(int64_t));
@@ -1275,10 +1350,10 @@ static int hostsim_solve_slabs_on(void** handles, int n, const mgc_transport* cb
     return x.error ? 100 + x.error : rc;
 }
 
-extern "C" int hostsim_solve_slabs(void** handles, int n, int ndir, const mgc_transport* cb, const int64_t* params, int64_t* stats_out)
+extern "C" int hostsim_solve_slabs(void** handles, int n, int ndir, const mgc_transport* cb, const int64_t* params, int nparams, int64_t* stats_out)
 {
-    if (ndir == 26) return hostsim_solve_slabs_on<HostDev26>(handles, n, cb, params, mgc_layout26(), 26, stats_out);
-    return hostsim_solve_slabs_on<HostDev>(handles, n, cb, params, mgc_layout6(), 6, stats_out);
+    if (ndir == 26) return hostsim_solve_slabs_on<HostDev26>(handles, n, cb, params, nparams, mgc_layout26(), 26, stats_out);
+    return hostsim_solve_slabs_on<HostDev>(handles, n, cb, params, nparams, mgc_layout6(), 6, stats_out);
 }
 
 extern "C" void hostsim_set_halo_max(void* h, int which, int n)

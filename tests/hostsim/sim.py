@@ -71,14 +71,60 @@ def prof():
     return out
 
 
-def solve(shape, weights, trcap, rounds=0, cycles=0, sweeps=0, max_outer=0, wave_mode=None):
-    """weights: per-axis arrays for a 3-D shape (oracle layout); returns (labels[bool array], stats dict)."""
+# The schedule knobs of MgcSolveParams (mgc_driver.inl), in the order of hostsim.cpp:hostsim_params.  Every entry point below forwards
+# all of them by name and refuses any other name: a knob is never accepted and then ignored.
+SCHEDULE_KNOBS = ("rounds_per_relabel", "max_cycles", "max_sweeps", "max_outer", "incremental_relabel", "exchange_passes", "radial",
+                  "exchange_rounds", "check_rounds", "relabel_batch", "stop_below", "adaptive_rounds", "radial_min_c", "radial_rounds0",
+                  "radial_budget_x16", "trace")
+_KEEP = np.iinfo(np.int64).min  # hostsim.cpp:HOSTSIM_KEEP, the default of the neighbourhood
+
+
+def _knob_vector(knobs):
+    n = lib().hostsim_param_count()
+    if n != len(SCHEDULE_KNOBS):
+        raise RuntimeError("SCHEDULE_KNOBS names %d knobs, hostsim.cpp:hostsim_params takes %d: keep the two lists in step" % (len(SCHEDULE_KNOBS), n))
+    unknown = sorted(set(knobs) - set(SCHEDULE_KNOBS))
+    if unknown:
+        raise TypeError("the host simulator has no schedule knob %s (it takes %s)" % (", ".join(unknown), ", ".join(SCHEDULE_KNOBS)))
+    return np.asarray([_KEEP if knobs.get(k) is None else int(knobs[k]) for k in SCHEDULE_KNOBS], np.int64)
+
+
+def _check_knobs(rc, p):
+    if rc < -len(SCHEDULE_KNOBS):
+        raise ValueError("the host simulator refuses a parameter vector of %d entries" % p.size)
+    if rc < 0:
+        raise ValueError("the host simulator refuses %s=%d (mgc_set_param's range)" % (SCHEDULE_KNOBS[-rc - 1], int(p[-rc - 1])))
+    return rc
+
+
+def _legacy_knobs(knobs, rounds, cycles, sweeps, max_outer, cycles_below_zero):
+    """the positional arguments of solve / solve26 (0: the default) as knobs; an explicit knob of the same name wins"""
+    out = {}
+    if rounds > 0:
+        out["rounds_per_relabel"] = rounds
+    if cycles > 0 or (cycles_below_zero and cycles < 0):
+        out["max_cycles"] = cycles
+    if sweeps > 0:
+        out["max_sweeps"] = sweeps
+    if max_outer < 0 and not cycles_below_zero:  # (6-neighbourhood: negative = from-scratch relabels only, A/B tests)
+        out["incremental_relabel"] = 0
+        max_outer = -max_outer - 1
+    if max_outer > 0:
+        out["max_outer"] = max_outer
+    out.update(knobs)
+    return out
+
+
+def solve(shape, weights, trcap, rounds=0, cycles=0, sweeps=0, max_outer=0, wave_mode=None, **knobs):
+    """weights: per-axis arrays for a 3-D shape (oracle layout); returns (labels[bool array], stats dict).
+    ``knobs``: any of SCHEDULE_KNOBS by name (others raise TypeError, values mgc_set_param refuses ValueError)."""
     if wave_mode is not None:
         set_wave_mode(wave_mode)
         try:
-            return solve(shape, weights, trcap, rounds, cycles, sweeps, max_outer)
+            return solve(shape, weights, trcap, rounds, cycles, sweeps, max_outer, **knobs)
         finally:
             set_wave_mode(0)
+    p = _knob_vector(_legacy_knobs(knobs, rounds, cycles, sweeps, max_outer, False))
     shape = np.asarray(shape, dtype=np.int64)
     assert shape.size == 3
     ws = [np.ascontiguousarray(w, dtype=np.float64).ravel() for w in weights]
@@ -86,7 +132,12 @@ def solve(shape, weights, trcap, rounds=0, cycles=0, sweeps=0, max_outer=0, wave
     tr = np.ascontiguousarray(trcap, dtype=np.float64).ravel()
     labels = np.empty(int(np.prod(shape)), np.uint8)
     stats = np.zeros(16, np.int64)
-    rc = lib().hostsim_solve(shape, ws[0], ws[1], ws[2], tr, rounds, cycles, sweeps, max_outer, labels, stats)
+    L = lib()
+    pf = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
+    L.hostsim_solve_p.restype = C.c_int
+    L.hostsim_solve_p.argtypes = [np.ctypeslib.ndpointer(np.int64), pf, pf, pf, pf, np.ctypeslib.ndpointer(np.int64), C.c_int,
+                                  np.ctypeslib.ndpointer(np.uint8), np.ctypeslib.ndpointer(np.int64)]
+    rc = _check_knobs(L.hostsim_solve_p(shape, ws[0], ws[1], ws[2], tr, p, p.size, labels, stats), p)
     st = dict(zip(STAT_NAMES, stats.tolist()))
     st["rc"] = rc
     return labels.reshape(tuple(shape)), st
@@ -121,22 +172,14 @@ def _solve_group(slabs, transport, params, ndir):
     from medpy_amd.slab import HostTransport
     from medpy_amd import _lib as hip
     L = lib()
+    p = _knob_vector(params)
     L.hostsim_solve_slabs.restype = C.c_int
     L.hostsim_solve_slabs.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.POINTER(hip.Transport), np.ctypeslib.ndpointer(np.int64),
-                                      np.ctypeslib.ndpointer(np.int64)]
-    p = np.zeros(8, np.int64)
-    p[0] = params.get("rounds_per_relabel", 0)
-    p[1] = params.get("max_cycles", 0)
-    p[2] = params.get("max_sweeps", 0)
-    p[3] = params.get("max_outer", 0)
-    p[4] = params.get("incremental_relabel", 1)
-    p[5] = params.get("exchange_passes", 0)
-    p[6] = params.get("radial", -1)
-    p[7] = params.get("exchange_rounds", 0)
+                                      C.c_int, np.ctypeslib.ndpointer(np.int64)]
     hs = (C.c_void_p * len(slabs))(*[s._h for s in slabs])
     st = np.zeros(16, np.int64)
     cb = HostTransport(transport) if transport is not None else None
-    rc = L.hostsim_solve_slabs(hs, len(slabs), ndir, C.byref(cb.struct) if cb else None, p, st)
+    rc = _check_knobs(L.hostsim_solve_slabs(hs, len(slabs), ndir, C.byref(cb.struct) if cb else None, p, p.size, st), p)
     if cb is not None and cb.error is not None:
         raise cb.error
     assert rc in (0, 1), "hostsim_solve_slabs failed (%d)" % rc
@@ -242,27 +285,28 @@ def weights26(shape, weights_by_offset):
     return w
 
 
-def solve26(shape, weights_by_offset, trcap, rounds=0, cycles=0, sweeps=0, max_outer=0, wave_mode=None):
+def solve26(shape, weights_by_offset, trcap, rounds=0, cycles=0, sweeps=0, max_outer=0, wave_mode=None, **knobs):
+    """26-neighbourhood: weights_by_offset = {offset: array (NaN where no neighbour)} for the 13 forward offsets
+    (oracle/energy_numpy.py:boundary_weights_offsets).  Returns (labels, stats).  ``knobs``: as solve()."""
     if wave_mode is not None:  # bit 4 (16): the discharge runs one wave per tile (mgc_wave_ops26.inl)
         set_wave_mode(wave_mode)
         try:
-            return solve26(shape, weights_by_offset, trcap, rounds, cycles, sweeps, max_outer)
+            return solve26(shape, weights_by_offset, trcap, rounds, cycles, sweeps, max_outer, **knobs)
         finally:
             set_wave_mode(0)
-    """26-neighbourhood: weights_by_offset = {offset: array (NaN where no neighbour)} for the 13 forward offsets
-    (oracle/energy_numpy.py:boundary_weights_offsets).  Returns (labels, stats)."""
+    p = _knob_vector(_legacy_knobs(knobs, rounds, cycles, sweeps, max_outer, True))
     L = lib()
     pf = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
-    L.hostsim_solve26.restype = C.c_int
-    L.hostsim_solve26.argtypes = [np.ctypeslib.ndpointer(np.int64), pf, pf, C.c_int, C.c_int, C.c_int, C.c_int,
-                                  np.ctypeslib.ndpointer(np.uint8), np.ctypeslib.ndpointer(np.int64)]
+    L.hostsim_solve26_p.restype = C.c_int
+    L.hostsim_solve26_p.argtypes = [np.ctypeslib.ndpointer(np.int64), pf, pf, np.ctypeslib.ndpointer(np.int64), C.c_int,
+                                    np.ctypeslib.ndpointer(np.uint8), np.ctypeslib.ndpointer(np.int64)]
     shape = tuple(int(v) for v in shape)
     n = int(np.prod(shape))
     w = weights26(shape, weights_by_offset)
     labels = np.empty(n, np.uint8)
     stats = np.zeros(16, np.int64)
-    rc = L.hostsim_solve26(np.asarray(shape, np.int64), np.ascontiguousarray(w).ravel(), np.ascontiguousarray(trcap, dtype=np.float64).ravel(),
-                           rounds, cycles, sweeps, max_outer, labels, stats)
+    rc = _check_knobs(L.hostsim_solve26_p(np.asarray(shape, np.int64), np.ascontiguousarray(w).ravel(),
+                                          np.ascontiguousarray(trcap, dtype=np.float64).ravel(), p, p.size, labels, stats), p)
     st = dict(zip(STAT_NAMES, stats.tolist()))
     st["rc"] = rc
     return labels.reshape(shape), st
