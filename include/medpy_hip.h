@@ -72,14 +72,16 @@ typedef struct mgc_stats {
     int64_t ntiles;
     int64_t nvox;
     int64_t device_bytes;      /* HBM held by the handle                                   */
-    int64_t reserved[3];       /* [0]: counter read-backs (host syncs) of the solve; [1]: cycles of colour phases that ran on radial labels */
+    int64_t reserved[3];       /* [0]: counter read-backs (host syncs) of the solve; [1]: cycles of colour phases that ran on radial labels; [2]: tiles a surface of weak arcs passes through, as built */
     /* the dominant kernel by itself: discharge_ms / _launches / _tiles pool the one-wave-per-tile kernel (k_discharge_w) and the
      * workgroup-per-tile kernel that takes the short lists; these three are k_discharge_w alone */
     double  discharge_wave_ms;
     int64_t discharge_wave_launches;
     int64_t discharge_wave_tiles;
     int64_t timing_stride;     /* every n-th solver launch of a kind carries a HIP event pair; the _ms are their mean x launches */
-    double  update_ms;         /* device time of the last t-link update (mgc_update_*): k_update_tlinks + its flow-constant sum; 0 after mgc_build */
+    double  update_ms;         /* device time of the last t-link update (mgc_update_*): k_update_tlinks + its flow-constant sum; 0 after mgc_build.
+                                  After mgc_edit_markers: plus its scatter kernel */
+    double  delta_ms;          /* device time of the last mgc_labels_delta: compare + count + scan (+ the ordered write when the ids were delivered) */
 } mgc_stats;
 
 /* Invariants of a maximum preflow, checked on the device (mgc_validate).  The reference has the same idea as a debugging
@@ -162,6 +164,38 @@ int mgc_set_markers(mgc_handle h, const uint8_t* fg, const uint8_t* bg);
  * mgc_set_regional_probability + mgc_build remain the cold rebuild. */
 int mgc_update_markers(mgc_handle h, const uint8_t* fg, const uint8_t* bg);
 int mgc_update_regional_probability(mgc_handle h, const void* probability_map, int dtype, double alpha);
+
+/* EDITS BY LIST: the two ends of the interactive loop at the cost of the edit, not of the volume.
+ *
+ * mgc_edit_markers replaces set_source_nodes / set_sink_nodes called with node ids (generate.py:169-172) on a graph that is
+ * already built: ids[k] = C-order flat voxel id, ops[k] = what happens to its markers: 1 = set the foreground marker, 2 = set the
+ * background marker, 4 = clear the foreground marker, 8 = clear the background marker, or a sum of these (a voxel may carry both
+ * markers, as with masks).  The mask planes resident in HBM are edited there by a scatter kernel -- 9 n bytes go up, a handle
+ * built without one kind of marker gets a zeroed plane of that kind first -- and the new t-links are folded into the residual
+ * state exactly as by mgc_update_markers: the handle is afterwards in the state mgc_update_markers with the equivalent full masks
+ * leaves it in, and a later mgc_build (cold rebuild) sees the edited masks.  States as for mgc_update_markers (MGC_ERR_STATE
+ * before mgc_build, after a solve that did not converge, on a slab handle).  MGC_ERR_INVALID, with mgc_last_error naming the first
+ * offending entry, for an id outside [0, nvox), ops == 0, ops > 15, set and clear of the same marker in one entry (1|4, 2|8) and
+ * for an id that is in the list twice; a refused call leaves the handle exactly as it was.  The list is checked on the host before
+ * anything is written (a list that does not ascend strictly is sorted in a copy to find repeated ids): an edit of more than a
+ * fraction of the volume is better sent as masks.  n == 0 is MGC_OK and changes nothing, a finished solve included.
+ *   If the handle holds a finished solve when the edit arrives, the label volume of that solve is first put aside in HBM (one
+ * byte per voxel, allocated on the first such call and kept with the handle; MGC_ERR_OOM before anything changed if it cannot be
+ * had).  Further edits before the next solve keep that copy.  mgc_build, mgc_update_markers and mgc_update_regional_probability
+ * drop it.
+ *
+ * mgc_get_markers: the resident masks, 0 / 1 per voxel; either pointer may be NULL, a kind the handle does not hold reads as
+ * zeros.  How a caller who only ever sent lists saves a session.
+ *
+ * mgc_labels_delta replaces the what_segment loop over all voxels (bin/medpy_graphcut_voxel.py:177-181) after an edit: after
+ * mgc_maxflow on a handle that holds the labels of the solve before the edit(s), *n = the number of voxels whose label differs
+ * from that solve's, and if *n <= cap, ids[0 .. *n) = their flat ids in ascending order (a label is one bit: new = old ^ 1).  If
+ * *n > cap nothing is written to ids and the call still returns MGC_OK: size a buffer and ask again, or fall back to mgc_labels.
+ * The two label volumes are compared on the device; 8 *n bytes and the count come down.  Changes no state, may be repeated.
+ * MGC_ERR_STATE when the handle is not solved or holds no such labels. */
+int mgc_edit_markers(mgc_handle h, int64_t n, const int64_t* ids, const uint8_t* ops);
+int mgc_get_markers(mgc_handle h, uint8_t* fg, uint8_t* bg);
+int mgc_labels_delta(mgc_handle h, int64_t cap, int64_t* ids, int64_t* n);
 
 /* After mgc_maxflow (or the slab driver's last step): see mgc_validation.  Also works on a graph whose solve was cut
  * short (MGC_ERR_NOT_CONVERGED): it then reports the excess that is still active.  MGC_ERR_STATE before the first solve

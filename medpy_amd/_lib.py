@@ -32,7 +32,7 @@ class Stats(C.Structure):
         ("relabel_tiles", C.c_int64), ("global_relabels", C.c_int64), ("phases", C.c_int64), ("ntiles", C.c_int64),
         ("nvox", C.c_int64), ("device_bytes", C.c_int64), ("reserved", C.c_int64 * 3),
         ("discharge_wave_ms", C.c_double), ("discharge_wave_launches", C.c_int64), ("discharge_wave_tiles", C.c_int64),
-        ("timing_stride", C.c_int64), ("update_ms", C.c_double),
+        ("timing_stride", C.c_int64), ("update_ms", C.c_double), ("delta_ms", C.c_double),
     ]
 
     def as_dict(self):
@@ -128,6 +128,9 @@ SIGNATURES = {
     "mgc_set_markers": (_INT, [_VP, _VP, _VP]),
     "mgc_update_markers": (_INT, [_VP, _VP, _VP]),
     "mgc_update_regional_probability": (_INT, [_VP, _VP, _INT, _DBL]),
+    "mgc_edit_markers": (_INT, [_VP, _I64, _VP, _VP]),
+    "mgc_get_markers": (_INT, [_VP, _VP, _VP]),
+    "mgc_labels_delta": (_INT, [_VP, _I64, _VP, C.POINTER(_I64)]),
     "mgc_add_edges": (_INT, [_VP, _I64, _VP, _VP, _VP, _VP]),
     "mgc_set_tweights_merged": (_INT, [_VP, _VP, _DBL]),
     "mgc_build": (_INT, [_VP]),

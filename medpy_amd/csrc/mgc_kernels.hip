@@ -45,6 +45,7 @@
 #include "mgc_brick_ops.inl"
 #include "mgc_terms.h"
 #include "mgc_driver.inl"
+#include "mgc_edit_ops.inl"
 
 #define MGC_MARKER_MAX 65535.0              /* GCGraph.MAX, graph.py:288-291 */
 
@@ -2613,6 +2614,10 @@ struct mgc_graph {
     int32_t* h_count = nullptr; /* pinned */
     double* h_scalar = nullptr; /* pinned */
     uint8_t* h_labels = nullptr; bool labels_on_host = false;
+    /* mgc_edit_markers: the labels of the solve the handle held when the first list edit since then arrived (C order, one byte per
+     * voxel), allocated on first use; mgc_labels_delta compares the next solve's labels with it.  It and d_labels change hands at
+     * such an edit. */
+    uint8_t* d_labels_prev = nullptr; bool has_prev = false;
     bool built = false, solved = false;
     bool unconverged = false;  /* the last solve of this build stopped at MGC_ERR_NOT_CONVERGED: warm updates are refused until the next mgc_build */
     bool labels_valid = false; /* the distance labels belong to this build (set by the first label fill of a solve, cleared by mgc_build) */
@@ -4020,7 +4025,7 @@ int mgc_destroy(mgc_handle h)
     void* ptrs[] = {L.rcap, L.cap0, L.excess, L.sink, L.height, L.rmask, L.rmask32, L.obox, L.oflags, L.list[0], L.list[1], L.list[2],
                     L.list[3], L.list[4], L.list[5], L.list[6], L.list[7], L.list[8], L.list[9], L.list[10], L.list[11], L.list[12],
                     L.list[13], L.list[14], L.list[15], L.list[16], L.list[17], L.count, L.stamp, L.rstamp, L.status, h->d_tr0, h->d_part, h->d_part2, h->d_scalar,
-                    h->d_labels, h->d_tflags, h->d_tsum, h->d_image, h->d_lut, h->d_prob, h->d_fg, h->d_bg, h->d_tr_in, h->d_eslot, h->d_eval, h->d_erun, L.hshadow[0], L.hshadow[1], h->d_vout, h->d_dt16, h->d_ds16, h->d_hexact, h->d_halo, h->d_xchg[0], h->d_xchg[1], h->d_xchg[2], h->d_xchg[3], h->d_cnt64, h->d_carry[0], h->d_carry[1], h->d_carry_in[0], h->d_carry_in[1]};
+                    h->d_labels, h->d_labels_prev, h->d_tflags, h->d_tsum, h->d_image, h->d_lut, h->d_prob, h->d_fg, h->d_bg, h->d_tr_in, h->d_eslot, h->d_eval, h->d_erun, L.hshadow[0], L.hshadow[1], h->d_vout, h->d_dt16, h->d_ds16, h->d_hexact, h->d_halo, h->d_xchg[0], h->d_xchg[1], h->d_xchg[2], h->d_xchg[3], h->d_cnt64, h->d_carry[0], h->d_carry[1], h->d_carry_in[0], h->d_carry_in[1]};
     for (void* p : ptrs)
         if (p) (void)mgc_dfree(p);
     if (h->h_count) (void)hipHostFree(h->h_count);
@@ -4279,6 +4284,7 @@ int mgc_update_markers(mgc_handle h, const uint8_t* fg, const uint8_t* bg)
     if (!h) return MGC_ERR_INVALID;
     { const int rc = mgc_update_check(h, "mgc_update_markers"); if (rc) return rc; }
     MGC_HIP(h, hipSetDevice(h->device));
+    h->has_prev = false;
     int rc = MGC_OK;
     if (fg) rc = mgc_upload(h, (void**)&h->d_fg, fg, (size_t)h->nvox);
     else if (h->d_fg) { (void)mgc_dfree(h->d_fg); h->d_fg = nullptr; }
@@ -4295,12 +4301,168 @@ int mgc_update_regional_probability(mgc_handle h, const void* pm, int dtype, dou
     { const int rc = mgc_update_check(h, "mgc_update_regional_probability"); if (rc) return rc; }
     if (!pm || (dtype != MGC_F32 && dtype != MGC_F64)) return mgc_fail(h, MGC_ERR_INVALID, "probability map must be float32 or float64");
     MGC_HIP(h, hipSetDevice(h->device));
+    h->has_prev = false;
     if (h->d_prob && h->prob_dtype != dtype) { (void)mgc_dfree(h->d_prob); h->d_prob = nullptr; }
     h->prob_dtype = dtype;
     h->alpha = alpha;
     const int rc = mgc_upload(h, &h->d_prob, pm, (size_t)h->nvox * mgc_dtype_size(dtype));
     if (rc) return rc;
     return mgc_update_tlinks(h);
+}
+
+/* ---- edits by list ("Edits by list"): kernels in mgc_edit_ops.inl ---- */
+
+/* Device scratch of a call: the per-tile partials h->d_part (scratch of the cut value, the fold and mgc_validate, nothing in it
+ * lives from one call to the next) from byte `skip` on where `bytes` fit behind it, else a block of its own (*own, to be freed by
+ * the caller).  A stroke of a few dozen ids and the few dozen ids of the labels it flips never leave d_part. */
+static int mgc_call_scratch(mgc_handle h, size_t skip, size_t bytes, void** p, void** own)
+{
+    const size_t cap = (size_t)(h->L.ntiles > 4096 ? h->L.ntiles : 4096) * sizeof(double);
+    *own = nullptr;
+    skip = (skip + 15) & ~(size_t)15;
+    if (skip + bytes <= cap) { *p = (char*)h->d_part + skip; return MGC_OK; }
+    MGC_HIP(h, mgc_dmalloc(own, bytes));
+    *p = *own;
+    return MGC_OK;
+}
+
+/* a zeroed mask plane for a handle that holds none of that kind, kept the way mgc_upload keeps it */
+static int mgc_zero_plane(mgc_handle h, uint8_t** dst)
+{
+    if (*dst) return MGC_OK;
+    MGC_HIP(h, mgc_dmalloc((void**)dst, (size_t)h->nvox));
+    h->device_bytes += h->nvox;
+    h->buf_cap[(const void*)dst] = (size_t)h->nvox;
+    MGC_HIP(h, hipMemsetAsync(*dst, 0, (size_t)h->nvox, h->stream));
+    return MGC_OK;
+}
+
+int mgc_edit_markers(mgc_handle h, int64_t n, const int64_t* ids, const uint8_t* ops)
+{
+    if (!h) return MGC_ERR_INVALID;
+    { const int rc = mgc_update_check(h, "mgc_edit_markers"); if (rc) return rc; }
+    if (n < 0 || (n > 0 && (!ids || !ops))) return mgc_fail(h, MGC_ERR_INVALID, "mgc_edit_markers: n = %lld, ids / ops NULL", (long long)n);
+    if (n == 0) return MGC_OK;
+    /* every check before the first write: a refused call leaves the handle as it was */
+    bool set_fg = false, set_bg = false;
+    for (int64_t k = 0; k < n; ++k) {
+        const unsigned op = ops[k];
+        if (ids[k] < 0 || ids[k] >= h->nvox) return mgc_fail(h, MGC_ERR_INVALID, "mgc_edit_markers: entry %lld: id %lld outside [0, %lld)", (long long)k, (long long)ids[k], (long long)h->nvox);
+        if (op == 0 || op > 15) return mgc_fail(h, MGC_ERR_INVALID, "mgc_edit_markers: entry %lld (id %lld): ops %u is not a combination of 1, 2, 4, 8", (long long)k, (long long)ids[k], op);
+        if ((op & 5u) == 5u || (op & 10u) == 10u) return mgc_fail(h, MGC_ERR_INVALID, "mgc_edit_markers: entry %lld (id %lld): ops %u sets and clears the same marker", (long long)k, (long long)ids[k], op);
+        set_fg |= (op & MGC_EDIT_SET_FG) != 0;
+        set_bg |= (op & MGC_EDIT_SET_BG) != 0;
+    }
+    {
+        bool sorted = true;
+        for (int64_t k = 1; k < n && sorted; ++k) sorted = ids[k - 1] < ids[k];
+        if (!sorted) { /* (strictly ascending lists, what the Python layer sends, are done) */
+            std::vector<std::pair<int64_t, int64_t>> byid((size_t)n);
+            for (int64_t k = 0; k < n; ++k) byid[(size_t)k] = {ids[k], k};
+            std::sort(byid.begin(), byid.end());
+            int64_t first = -1;
+            for (int64_t k = 1; k < n; ++k)
+                if (byid[(size_t)k].first == byid[(size_t)k - 1].first && (first < 0 || byid[(size_t)k].second < first)) first = byid[(size_t)k].second;
+            if (first >= 0) return mgc_fail(h, MGC_ERR_INVALID, "mgc_edit_markers: entry %lld: id %lld is in the list twice", (long long)first, (long long)ids[first]);
+        }
+    }
+    MGC_HIP(h, hipSetDevice(h->device));
+    MgcRange range_("mgc_edit_markers");
+    /* what can fail for want of memory comes first */
+    if (h->solved && !h->d_labels_prev) { const int rc = mgc_alloc(h, &h->d_labels_prev, h->nvox); if (rc) return rc; }
+    void* d_list = nullptr; void* own = nullptr;
+    const size_t ops_at = (size_t)n * sizeof(int64_t);
+    { const int rc = mgc_call_scratch(h, 0, ops_at + (size_t)n, &d_list, &own); if (rc) return rc; }
+    int rc = MGC_OK;
+    if (set_fg) rc = mgc_zero_plane(h, &h->d_fg);
+    if (!rc && set_bg) rc = mgc_zero_plane(h, &h->d_bg);
+    if (rc) { (void)mgc_dfree(own); return rc; }
+    if (h->solved) {
+        /* The labels of the finished solve: what mgc_labels_delta holds the next solve against.  Nothing reads d_labels between an
+         * update of the t-links and the next read-out, which writes every voxel of it -- so the copy aside is the two buffers changing
+         * hands, not 2 x nvox bytes through HBM.  Further edits before that solve find the handle unsolved and keep the copy. */
+        std::swap(h->d_labels, h->d_labels_prev);
+        h->has_prev = true;
+    }
+    hipError_t e = hipMemcpyAsync(d_list, ids, ops_at, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync((char*)d_list + ops_at, ops, (size_t)n, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipEventRecord(h->ev[2], h->stream);
+    if (e == hipSuccess) {
+        const int64_t wgs = (n + 255) / 256;
+        hipLaunchKernelGGL(k_edit_markers, dim3((unsigned)(wgs < 4096 ? wgs : 4096)), dim3(256), 0, h->stream, n, h->nvox, (const int64_t*)d_list,
+                           (const uint8_t*)d_list + ops_at, h->d_fg, h->d_bg);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(h->ev[3], h->stream);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(h->stream); (void)mgc_dfree(own); MGC_HIP(h, e); }
+    rc = mgc_update_tlinks(h); /* (waits for the stream: the list is consumed) */
+    (void)mgc_dfree(own);
+    if (rc) return rc;
+    float ms = 0.f;
+    MGC_HIP(h, hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
+    h->stats.update_ms += ms;
+    return MGC_OK;
+}
+
+int mgc_get_markers(mgc_handle h, uint8_t* fg, uint8_t* bg)
+{
+    if (!h) return MGC_ERR_INVALID;
+    MGC_HIP(h, hipSetDevice(h->device));
+    uint8_t* const out[2] = {fg, bg};
+    const uint8_t* const plane[2] = {h->d_fg, h->d_bg};
+    for (int k = 0; k < 2; ++k) {
+        if (!out[k]) continue;
+        if (!plane[k]) { memset(out[k], 0, (size_t)h->nvox); continue; }
+        MGC_HIP(h, mgc_staged_copy(h, const_cast<uint8_t*>(plane[k]), out[k], (size_t)h->nvox, false));
+        for (int64_t i = 0; i < h->nvox; ++i) out[k][i] = out[k][i] ? 1 : 0; /* (masks handed over as bytes count as "non-zero") */
+    }
+    return MGC_OK;
+}
+
+int mgc_labels_delta(mgc_handle h, int64_t cap, int64_t* ids, int64_t* n)
+{
+    if (!h || !n || cap < 0 || (cap > 0 && !ids)) return MGC_ERR_INVALID;
+    if (!h->solved) return mgc_fail(h, MGC_ERR_STATE, "mgc_labels_delta before mgc_maxflow");
+    if (!h->has_prev) return mgc_fail(h, MGC_ERR_STATE, "mgc_labels_delta: no labels of a previous solve are kept (they are from the first mgc_edit_markers after a solve on; mgc_build and the mask / regional updates drop them)");
+    MGC_HIP(h, hipSetDevice(h->device));
+    MgcRange range_("mgc_labels_delta");
+    const int64_t nseg = (h->nvox + MGC_DELTA_SEG - 1) / MGC_DELTA_SEG;
+    const size_t off_bytes = (size_t)(nseg + 1) * sizeof(unsigned long long);
+    void* p = nullptr; void* own = nullptr;
+    { const int rc = mgc_call_scratch(h, 0, off_bytes, &p, &own); if (rc) return rc; }
+    if (own) { (void)mgc_dfree(own); return mgc_fail(h, MGC_ERR_UNSUPPORTED, "mgc_labels_delta: %lld segments do not fit the handle's scratch", (long long)nseg); } /* (cannot happen: a tile is 512 voxels, a segment 16384) */
+    unsigned long long* const d_off = (unsigned long long*)p;
+    const int64_t wgs = (nseg + 3) / 4;
+    const unsigned grid = (unsigned)(wgs < 16384 ? wgs : 16384);
+    float ms = 0.f, ms2 = 0.f;
+    MGC_HIP(h, hipEventRecord(h->ev[2], h->stream));
+    hipLaunchKernelGGL(k_labels_delta_count, dim3(grid), dim3(256), 0, h->stream, (const uint8_t*)h->d_labels, (const uint8_t*)h->d_labels_prev, h->nvox, nseg, d_off);
+    hipLaunchKernelGGL(k_labels_delta_scan, dim3(1), dim3(MGC_SCAN_THREADS), 0, h->stream, d_off, nseg);
+    MGC_HIP(h, hipGetLastError());
+    MGC_HIP(h, hipEventRecord(h->ev[3], h->stream));
+    unsigned long long* const h_total = (unsigned long long*)(h->h_scalar + 7);
+    MGC_HIP(h, hipMemcpyAsync(h_total, d_off + nseg, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    MGC_HIP(h, hipStreamSynchronize(h->stream));
+    MGC_HIP(h, hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
+    const int64_t total = (int64_t)*h_total;
+    *n = total;
+    if (total > 0 && total <= cap) {
+        { const int rc = mgc_call_scratch(h, off_bytes, (size_t)total * sizeof(int64_t), &p, &own); if (rc) return rc; }
+        hipError_t e = hipEventRecord(h->ev[2], h->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_labels_delta_write, dim3(grid), dim3(256), 0, h->stream, (const uint8_t*)h->d_labels, (const uint8_t*)h->d_labels_prev, h->nvox, nseg,
+                               (const unsigned long long*)d_off, total, (int64_t*)p);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(h->ev[3], h->stream);
+        if (e == hipSuccess) e = mgc_staged_copy(h, p, ids, (size_t)total * sizeof(int64_t), false);
+        else (void)hipStreamSynchronize(h->stream);
+        (void)mgc_dfree(own);
+        MGC_HIP(h, e);
+        MGC_HIP(h, hipEventElapsedTime(&ms2, h->ev[2], h->ev[3]));
+    }
+    h->stats.delta_ms = (double)ms + (double)ms2;
+    return MGC_OK;
 }
 
 int mgc_validate(mgc_handle h, mgc_validation* out)
@@ -4415,6 +4577,7 @@ int mgc_build(mgc_handle h)
     MgcRange range_("mgc_build");
     MgcLattice& L = h->L;
     MgcBuildArgs A{};
+    h->has_prev = false; /* (the snapshot of mgc_edit_markers belongs to the build it was taken in) */
     A.image = h->d_image; A.img_dtype = h->img_dtype; A.term = h->d_image ? h->term : MGC_TERM_NONE;
     MGC_HIP(h, hipEventRecord(h->ev[0], h->stream));
     A.p0 = h->sigma;

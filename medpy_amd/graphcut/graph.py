@@ -89,6 +89,58 @@ def boundary_table(term, image, sigma, limit=65536):
     return boundary_table_for_range(term, sigma, facts[1], facts[2], limit)
 
 
+def _edit_ids(shape, ids, what):
+    """one argument of VoxelGraph.edit_markers as a sorted int64 array of distinct flat ids"""
+    if ids is None:
+        return numpy.empty(0, dtype=numpy.int64)
+    nodes = 1
+    for s in shape:
+        nodes *= int(s)
+    if isinstance(ids, tuple):   # per-axis index arrays, as numpy.nonzero returns them
+        if len(ids) != len(shape):
+            raise ValueError("%s: %d index arrays for a volume of %d axes" % (what, len(ids), len(shape)))
+        axes = [numpy.asarray(a) for a in ids]
+        if any(a.size and a.dtype.kind not in "iu" for a in axes):
+            raise ValueError("%s: index arrays must hold integers" % what)
+        if len({a.shape for a in axes}) != 1 or axes[0].ndim != 1:
+            raise ValueError("%s: index arrays must be 1-D and of one length" % what)
+        if not axes[0].size:
+            return numpy.empty(0, dtype=numpy.int64)
+        if any(int(a.min()) < 0 or int(a.max()) >= n for a, n in zip(axes, shape)):
+            raise ValueError("%s: index outside the volume of shape %s" % (what, tuple(shape)))
+        flat = numpy.ravel_multi_index(tuple(a.astype(numpy.int64) for a in axes), tuple(shape))
+    else:
+        flat = numpy.asarray(ids)
+        if flat.ndim != 1:
+            raise ValueError("%s: node ids must be a 1-D array (or a tuple of per-axis index arrays)" % what)
+        if not flat.size:
+            return numpy.empty(0, dtype=numpy.int64)
+        if flat.dtype.kind not in "iu":
+            raise ValueError("%s: node ids must be integers, not %s" % (what, flat.dtype))
+        if int(flat.min()) < 0 or int(flat.max()) >= nodes:
+            raise ValueError("%s: node id outside [0, %d)" % (what, nodes))
+    return numpy.unique(flat.astype(numpy.int64))
+
+
+def merge_marker_edits(shape, fg=None, bg=None, erase=None):
+    """The list VoxelGraph.edit_markers sends (mgc_edit_markers, include/medpy_hip.h): ``(ids, ops)``, ids ascending and distinct.
+
+    In mask terms the edit is ``fg' = (fg & ~erase) | fg_ids`` and ``bg' = (bg & ~erase) | bg_ids``.  Each argument is None, a
+    1-D integer array of flat (C-order) node ids, or a tuple of per-axis index arrays as ``numpy.nonzero`` returns.  An id in
+    several lists gets ONE entry: 1 = set fg, 2 = set bg, 4 = clear fg, 8 = clear bg; erase alone = 4|8, erase + fg = 1|8,
+    erase + bg = 2|4, fg + bg (with or without erase) = 1|2.  An id repeated inside a list counts once.  ValueError for ids
+    outside the volume, non-integer dtypes, and a tuple whose length is not the volume's ndim."""
+    shape = tuple(int(s) for s in shape)
+    parts = [(_edit_ids(shape, fg, "fg"), 1), (_edit_ids(shape, bg, "bg"), 2), (_edit_ids(shape, erase, "erase"), 12)]
+    ids = numpy.unique(numpy.concatenate([p for p, _ in parts]))
+    ops = numpy.zeros(ids.size, dtype=numpy.uint8)
+    for p, bits in parts:
+        ops[numpy.searchsorted(ids, p)] |= bits   # (p is distinct: a plain fancy-indexed |= sees every id once)
+    ops[(ops & 1) != 0] &= 0xff ^ 4   # set wins over erase
+    ops[(ops & 2) != 0] &= 0xff ^ 8
+    return ids, ops
+
+
 class VoxelGraph(object):
     """What ``graph_from_voxels`` returns: the stand-in for ``maxflow.GraphDouble``.
 
@@ -103,6 +155,11 @@ class VoxelGraph(object):
     kept, and the next ``maxflow()`` continues from it (warm solve).  ``maxflow()``, ``labels()`` and
     ``what_segment()`` then describe the cut of the new inputs -- the same labels and the same flow, bit for bit, as
     ``graph_from_voxels`` of those inputs.  Explicit edges and t-weights that plug-in terms set stay part of the graph.
+
+    A stroke of a few voxels need not cross the bus as two whole masks, nor its result as a whole label volume:
+    ``edit_markers(fg, bg, erase)`` edits the masks resident in HBM by lists of voxel ids, ``changed_labels()`` returns the ids
+    of the voxels whose label the next ``maxflow()`` changed, ``labels(out=previous)`` applies them to the caller's copy of the
+    previous labels, and ``markers()`` reads the resident masks back.
     """
 
     termtype = termtype
@@ -206,6 +263,35 @@ class VoxelGraph(object):
         self._labels = None
         self._call("mgc_update_regional_probability", _lib.ptr(prob), _lib.DTYPE_IDS[prob.dtype], float(alpha))
 
+    # -- edits by list
+    def edit_markers(self, fg=None, bg=None, erase=None):
+        """Edit the markers by voxel lists instead of whole masks: ``fg' = (fg & ~erase) | fg_ids``, ``bg' = (bg & ~erase) | bg_ids``
+        (see ``merge_marker_edits`` for the forms the arguments take).  Otherwise as ``update_markers``: the next ``maxflow()`` is
+        a warm solve.  If the graph holds a finished cut, its labels are kept on the device for ``changed_labels()``."""
+        ids, ops = merge_marker_edits(self._shape, fg, bg, erase)
+        self._call("mgc_edit_markers", ids.size, _lib.ptr(ids), _lib.ptr(ops))
+        if ids.size:
+            self._labels = None
+
+    def markers(self):
+        """(fg, bg): the markers the graph holds now, bool arrays of the volume's shape"""
+        fg = numpy.empty(self._nodes, dtype=numpy.uint8)
+        bg = numpy.empty(self._nodes, dtype=numpy.uint8)
+        self._call("mgc_get_markers", _lib.ptr(fg), _lib.ptr(bg))
+        return fg.view(numpy.bool_).reshape(self._shape), bg.view(numpy.bool_).reshape(self._shape)
+
+    def changed_labels(self):
+        """After ``edit_markers`` (one or several) and ``maxflow()``: ascending int64 array of the flat ids of the voxels whose
+        label differs from the cut the graph held before the first of those edits.  MedpyHipError (ERR_STATE) when the graph
+        holds no such earlier cut (never edited by list since it was built or updated by masks) or is not solved."""
+        n = C.c_int64(0)
+        ids = numpy.empty(1024, dtype=numpy.int64)   # a stroke flips a few dozen labels: one call; more: the count sizes the buffer
+        self._call("mgc_labels_delta", ids.size, _lib.ptr(ids), C.byref(n))
+        if n.value > ids.size:
+            ids = numpy.empty(n.value, dtype=numpy.int64)
+            self._call("mgc_labels_delta", ids.size, _lib.ptr(ids), C.byref(n))
+        return ids[:n.value].copy() if ids.size != n.value else ids
+
     def _add_edges(self, i, j, cap, rev):
         i = numpy.ascontiguousarray(i, dtype=numpy.int64)
         j = numpy.ascontiguousarray(j, dtype=numpy.int64)
@@ -238,9 +324,27 @@ class VoxelGraph(object):
         self._call("mgc_maxflow", C.byref(flow))
         return flow.value
 
-    def labels(self):
+    def labels(self, out=None):
         """All voxels at once: bool array of the marker shape, False where what_segment == SINK
-        (the loop of bin/medpy_graphcut_voxel.py:177-182)."""
+        (the loop of bin/medpy_graphcut_voxel.py:177-182).
+
+        ``out``: a writeable C-contiguous bool or uint8 array of the volume's shape that holds the labels of the previous cut
+        (what ``changed_labels()`` refers to).  Only the ids of the changed voxels are read from the device and ``out`` is
+        flipped there and returned; where the graph keeps no previous cut the whole volume is read into ``out``."""
+        if out is not None:
+            if not (isinstance(out, numpy.ndarray) and out.shape == self._shape and out.dtype in (numpy.bool_, numpy.uint8)
+                    and out.flags.c_contiguous and out.flags.writeable):
+                raise ValueError("labels(out=...): a writeable C-contiguous bool or uint8 array of shape %s" % (self._shape,))
+            flat = out.reshape(-1).view(numpy.uint8)
+            try:
+                ids = self.changed_labels()
+            except _lib.MedpyHipError as e:
+                if e.code != _lib.ERR_STATE:
+                    raise
+                self._call("mgc_labels", _lib.ptr(flat))   # (not solved: ERR_STATE again, from here)
+                return out
+            flat[ids] ^= 1
+            return out
         if self._labels is None:
             out = numpy.empty(self._nodes, dtype=numpy.uint8)
             self._call("mgc_labels", _lib.ptr(out))
@@ -369,6 +473,21 @@ class SparseGraph(object):
         """Warm updates exist for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
         raise NotImplementedError("medpy_amd: update_regional_term is implemented for the voxel lattice solver (1-D..3-D volumes, "
                                   "VoxelGraph) only; this graph went to the sparse-graph solver: build it again from the new inputs")
+
+    def edit_markers(self, fg=None, bg=None, erase=None):
+        """Edits by list exist for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
+        raise NotImplementedError("medpy_amd: edit_markers is implemented for the voxel lattice solver (1-D..3-D volumes, "
+                                  "VoxelGraph) only; this graph went to the sparse-graph solver: build it again from the new inputs")
+
+    def changed_labels(self):
+        """Edits by list exist for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
+        raise NotImplementedError("medpy_amd: changed_labels is implemented for the voxel lattice solver (1-D..3-D volumes, "
+                                  "VoxelGraph) only; this graph went to the sparse-graph solver: read labels()")
+
+    def markers(self):
+        """Edits by list exist for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
+        raise NotImplementedError("medpy_amd: markers is implemented for the voxel lattice solver (1-D..3-D volumes, "
+                                  "VoxelGraph) only; this graph went to the sparse-graph solver, which keeps merged t-links, not masks")
 
     def reset(self):
         """Graph::reset, reference graph.cpp:46-60 (wrapper.cpp:68): back to the state just after construction -- no nodes
@@ -729,6 +848,18 @@ class EmbeddedLatticeGraph(object):
     def update_regional_term(self, probability_map, alpha):
         raise NotImplementedError("medpy_amd: update_regional_term is not implemented for a graph whose boundary image has another "
                                   "shape than its markers (EmbeddedLatticeGraph): build it again with graph_from_voxels")
+
+    def edit_markers(self, fg=None, bg=None, erase=None):
+        raise NotImplementedError("medpy_amd: edit_markers is not implemented for a graph whose boundary image has another shape "
+                                  "than its markers (EmbeddedLatticeGraph): build it again with graph_from_voxels")
+
+    def changed_labels(self):
+        raise NotImplementedError("medpy_amd: changed_labels is not implemented for a graph whose boundary image has another shape "
+                                  "than its markers (EmbeddedLatticeGraph): read labels()")
+
+    def markers(self):
+        raise NotImplementedError("medpy_amd: markers is not implemented for a graph whose boundary image has another shape "
+                                  "than its markers (EmbeddedLatticeGraph)")
 
     def stats(self):
         return self._inner.stats()
