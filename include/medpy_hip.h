@@ -260,7 +260,9 @@ enum {
     MGC_LAUNCH_DISCHARGE26 = 5,   /* k26_discharge: grid grid26_dis (0: grid_cap)                         */
     MGC_LAUNCH_DISCHARGE26_V = 6, /* k26_discharge_v                                                       */
     MGC_LAUNCH_DISCHARGE26_W = 7, /* k26_discharge_w: one wave per tile, persistent grid wave_grid26      */
-    MGC_NLAUNCH = 8
+    MGC_LAUNCH_DT_AXIS = 8,       /* k_dt_axis: both scans of one axis of a distance transform            */
+    MGC_LAUNCH_DT_SCAN = 9,       /* k_dt_scan: one scan of one axis (first_relabel_dt = 2, long lines, the z scans of a slab) */
+    MGC_NLAUNCH = 10
 };
 int mgc_get_launch_counts(mgc_handle h, int64_t* out, int n);
 
@@ -284,7 +286,10 @@ enum {
     MGC_OP_ACTIVATE = 5,     /* a0 = phase                                  */
     MGC_OP_DISCHARGE = 6,    /* a0 = list, a1 = phase, a2 = max cycles, a3 = max sweeps */
     MGC_OP_SUSPECT_PASS = 7, /* one pass of the tile-level suspect closure (sets counter MGC_CNT_CHANGED = 21 when something changed) */
-    MGC_OP_RESET_SUSPECT = 8 /* a0 = next epoch, a1 = next list: suspect tiles -> labels INF, queued for relabelling */
+    MGC_OP_RESET_SUSPECT = 8, /* a0 = next epoch, a1 = next list: suspect tiles -> labels INF, queued for relabelling */
+    MGC_OP_FIRST_RELABEL = 9  /* the first global relabel of a solve by distance transform, on a single handle as built: a0 = 0 the transform towards
+                                 the sink, 1 also the radial labels; a1 = c_min (radial_min_c).  MGC_ERR_STATE where the transform does not apply.
+                                 Resets the launch counts; mgc_get_heights reads what it left. */
 };
 int mgc_create_slab(int ndim, const int64_t* global_shape, int connectivity, int device, int rank, int nranks, mgc_handle* out);
 /* info[0..1] = local plane range [first, last) in the global volume (ghost planes included), info[2..3] = owned
@@ -292,6 +297,9 @@ int mgc_create_slab(int ndim, const int64_t* global_shape, int connectivity, int
 int mgc_slab_info(mgc_handle h, int64_t* info8);
 int mgc_solver_op(mgc_handle h, int op, int64_t a0, int64_t a1, int64_t a2, int64_t a3);
 int mgc_read_counts(mgc_handle h, int32_t* out32); /* 32 counters */
+/* The distance labels of a single handle, one int32 per voxel in C order: which = 0 the array in use, 1 the one kept aside (the exact
+ * labels while the radial ones are in use; MGC_ERR_STATE before there is one). */
+int mgc_get_heights(mgc_handle h, int which, int32_t* out);
 int mgc_halo_bytes(mgc_handle h, int kind, int64_t* bytes);
 /* side 0 = lower / 1 = upper slab boundary; kind 0 = labels (relabel pass), 1 = labels + outbox flow (phase),
    2 = DIRTY / SUSPECT flags of the border tiles (suspect closure of an incremental relabel) */

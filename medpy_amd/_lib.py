@@ -43,8 +43,12 @@ class Stats(C.Structure):
         return d
 
 
+OP_FIRST_RELABEL = 9  # mgc_solver_op: the first global relabel by distance transform alone (MGC_OP_FIRST_RELABEL)
+HINF = 0x3f3f3f3f     # the label "cannot reach the sink" (MGC_HINF)
+
 # mgc_get_launch_counts: the kinds of solver launch, in the order of MGC_LAUNCH_* (include/medpy_hip.h)
-LAUNCH_KINDS = ("k_discharge", "k_discharge_w", "k_relabel_tile", "k_relabel_v", "k_relabel_w", "k26_discharge", "k26_discharge_v", "k26_discharge_w")
+LAUNCH_KINDS = ("k_discharge", "k_discharge_w", "k_relabel_tile", "k_relabel_v", "k_relabel_w", "k26_discharge", "k26_discharge_v", "k26_discharge_w",
+                "k_dt_axis", "k_dt_scan")
 
 
 class Validation(C.Structure):
@@ -154,6 +158,7 @@ SIGNATURES = {
     "mgc_slab_info": (_INT, [_VP, C.POINTER(_I64)]),
     "mgc_solver_op": (_INT, [_VP, _INT, _I64, _I64, _I64, _I64]),
     "mgc_read_counts": (_INT, [_VP, _VP]),
+    "mgc_get_heights": (_INT, [_VP, _INT, _VP]),
     "mgc_halo_bytes": (_INT, [_VP, _INT, C.POINTER(_I64)]),
     "mgc_halo_pack": (_INT, [_VP, _INT, _INT, _VP, _INT]),
     "mgc_halo_unpack": (_INT, [_VP, _INT, _INT, _VP, _INT, C.c_uint32, _INT]),

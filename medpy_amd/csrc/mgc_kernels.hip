@@ -999,6 +999,131 @@ __global__ __launch_bounds__(256) void k_dt_scan(MgcLattice L, const void* in, v
     }
 }
 
+/* Both scans of one axis in one launch: every voxel is read once and written once, where k_dt_scan forward + backward read and write it
+ * twice.  A tile line is split over W waves of one workgroup, wave j holding tiles [8 j, 8 j + 8) of the line -- 64 values per lane -- in
+ * registers.  Each wave scans its run forward and backward on its own, leaves the value at its two ends in LDS, and after ONE barrier
+ * folds the ends of the waves in front of it / behind it into what enters its run from either side:
+ *      result(p) = min( local(p),  entry_front + 1 + p,  entry_back + 64 - p )        p = 0 .. 63 inside the run.
+ * The same integers as mgc_dt_scan_line forward then backward: a min-plus scan saturated at every step is the saturated minimum, so the
+ * distances stay plain ints until they are clamped to MGC_DT_INF at the store; padding voxels and lanes outside the volume enter as "no
+ * seed" and leave as MGC_DT_INF / MGC_HINF (they lie behind the last real voxel of their line: nothing is relayed through them to a real one).
+ * in == out is legal: a wave stores only what it loaded itself.  LPB short lines share a workgroup (W * LPB waves); the loop over the
+ * groups of lines is uniform over the workgroup, so every wave meets the barrier equally often, and the LDS block alternates between two
+ * halves so that a wave a round ahead does not overwrite ends that are still being read.
+ * SEED / FINAL as k_dt_scan; no carry planes (the z scans of a slab stay two launches, MgcSlabGroup::transform). */
+#define MGC_DT_RUN 8    /* tiles of a line per wave */
+#define MGC_DT_MAXW 16  /* waves of the largest workgroup: lines of up to 128 tiles */
+#define MGC_DT_BIG (1 << 20)
+template <int AXIS, int SEED, int FINAL>
+__global__ __launch_bounds__(64 * MGC_DT_MAXW) void k_dt_axis(MgcLattice L, const void* in, void* out, int c_min, int32_t* hout, int W, int LPB)
+{
+    __shared__ int s_end[2][MGC_DT_MAXW][2][64];
+    const int l = (int)(threadIdx.x & 63u);
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int sub = wv / W, j = wv - sub * W; /* line of the group, run of the line */
+    const int n = mgc_dt_lines<AXIS>(L);
+    const int na = AXIS == 0 ? L.gx : (AXIS == 1 ? L.gy : L.gz);
+    const int64_t len = AXIS == 0 ? L.dx : (AXIS == 1 ? L.dy : L.dz);
+    const int t0 = j * MGC_DT_RUN;
+    const int nt = na - t0 < MGC_DT_RUN ? na - t0 : MGC_DT_RUN;
+    const int ngroups = (n + LPB - 1) / LPB;
+    int C = MGC_HINF;
+    if (FINAL == 2) { C = L.count[mgc_cnt_radial_c(L)]; if (C < c_min) C = MGC_HINF; }
+    int half = 0;
+    for (int grp = (int)blockIdx.x; grp < ngroups; grp += (int)gridDim.x, half ^= 1) {
+        const int line = grp * LPB + sub;
+        const bool have = line < n; /* (uniform over the wave; a wave without a line still meets the barrier) */
+        int v[MGC_DT_RUN][8];
+        int64_t room = 0; /* real voxels of this lane's line from the start of the run on (<= 0: none) */
+        if (have) {
+            int64_t cu, cv, du, dv; /* as in mgc_dt_scan_line */
+            if (AXIS == 0) { cu = (int64_t)(line / L.gy) * 8 + (l >> 3); cv = (int64_t)(line % L.gy) * 8 + (l & 7); du = L.dz; dv = L.dy; }
+            else if (AXIS == 1) { cu = (int64_t)(line / L.gx) * 8 + (l >> 3); cv = (int64_t)(line % L.gx) * 8 + (l & 7); du = L.dz; dv = L.dx; }
+            else { cu = (int64_t)(line / L.gx) * 8 + (l >> 3); cv = (int64_t)(line % L.gx) * 8 + (l & 7); du = L.dy; dv = L.dx; }
+            room = cu < du && cv < dv ? len - (int64_t)t0 * 8 : 0;
+            /* every load of the run goes out before the first value is needed */
+#pragma unroll
+            for (int g = 0; g < MGC_DT_RUN; ++g) {
+                const int tile = g < nt ? mgc_dt_tile<AXIS>(L, line, t0 + g) : -1;
+                if (tile >= 0 && (SEED != 2 || mgc_source_tile(L, tile))) { /* (excess is read in source tiles only: the others' 4 KiB stay where they are) */
+                    const int64_t base = (int64_t)tile * MGC_TV;
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        const int loc = mgc_dt_loc<AXIS>(l, i);
+                        if (SEED == 1) v[g][i] = (((const uint8_t*)in)[base + loc] & MGC_MASK_SINK) ? 1 : MGC_DT_INF;
+                        else if (SEED == 2) v[g][i] = ((const double*)in)[base + loc] > 0.0 ? 1 : MGC_DT_INF;
+                        else v[g][i] = ((const uint16_t*)in)[base + loc];
+                    }
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) v[g][i] = MGC_DT_INF;
+                }
+            }
+            int c = MGC_DT_BIG;
+#pragma unroll
+            for (int g = 0; g < MGC_DT_RUN; ++g)
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    if (g * 8 + i >= room) v[g][i] = MGC_DT_INF; /* padding: never a seed */
+                    c = v[g][i] < c + 1 ? v[g][i] : c + 1;
+                    v[g][i] = c;
+                }
+            c = MGC_DT_BIG;
+#pragma unroll
+            for (int g = MGC_DT_RUN - 1; g >= 0; --g)
+#pragma unroll
+                for (int i = 7; i >= 0; --i) {
+                    c = v[g][i] < c + 1 ? v[g][i] : c + 1;
+                    v[g][i] = c;
+                }
+            s_end[half][wv][0][l] = v[MGC_DT_RUN - 1][7]; /* what leaves the run at its back (only read where a run follows: a full run) */
+            s_end[half][wv][1][l] = v[0][0];              /* ... and at its front */
+        }
+        __syncthreads();
+        if (!have) continue;
+        int ef = MGC_DT_BIG, eb = MGC_DT_BIG; /* the scan values next to the run, in front of it and behind it */
+        for (int k = 0; k < j; ++k) { const int e = s_end[half][sub * W + k][0][l]; ef = e < ef + 64 ? e : ef + 64; }
+        for (int k = W - 1; k > j; --k) { const int e = s_end[half][sub * W + k][1][l]; eb = e < eb + 64 ? e : eb + 64; }
+        int hx[2][8]; /* FINAL 2: the exact labels, one tile ahead of the stores (which they may not overtake: the arrays could alias) */
+        if (FINAL == 2) {
+            const int64_t base = (int64_t)mgc_dt_tile<AXIS>(L, line, t0) * MGC_TV;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) hx[0][i] = L.height[base + mgc_dt_loc<AXIS>(l, i)];
+        }
+#pragma unroll
+        for (int g = 0; g < MGC_DT_RUN; ++g) {
+            if (g >= nt) break;
+            const int64_t base = (int64_t)mgc_dt_tile<AXIS>(L, line, t0 + g) * MGC_TV;
+            if (FINAL == 2 && g + 1 < nt) {
+                const int64_t nbase = (int64_t)mgc_dt_tile<AXIS>(L, line, t0 + g + 1) * MGC_TV;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) hx[(g + 1) & 1][i] = L.height[nbase + mgc_dt_loc<AXIS>(l, i)];
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int p = g * 8 + i, loc = mgc_dt_loc<AXIS>(l, i);
+                int val = v[g][i];
+                val = val < ef + 1 + p ? val : ef + 1 + p;
+                val = val < eb + 64 - p ? val : eb + 64 - p;
+                if (val > MGC_DT_INF || p >= room) val = MGC_DT_INF;
+                if (FINAL == 1) ((int32_t*)out)[base + loc] = val < MGC_DT_INF ? val : MGC_HINF;
+                else ((uint16_t*)out)[base + loc] = (uint16_t)val;
+                if (FINAL == 2 && (hout || (C < MGC_HINF && val < MGC_DT_INF))) { /* the labels lowered on the way, as mgc_dt_scan_line does */
+                    const int hv = hx[g & 1][i];
+                    int nv = hv;
+                    if (C < MGC_HINF && val < MGC_DT_INF) {
+                        int gl = C - mgc_radial_steps(L, val - 1);
+                        gl = gl < 1 ? 1 : gl;
+                        if (hv < MGC_HINF && gl < hv) nv = gl;
+                    }
+                    if (hout) hout[base + loc] = nv;
+                    else if (nv != hv) L.height[base + loc] = nv;
+                }
+            }
+        }
+    }
+}
+
 /* Z-slabs: the shadows of the border labels after a transform that ran on both sides of every border (mgc_shadow_sync_tile) */
 __global__ __launch_bounds__(256) void k_shadow_sync(MgcLattice L)
 {
@@ -2932,6 +3057,30 @@ struct HipDevT {
         time_end(id);
         relabel_launches++;
     }
+    /* One axis of a distance transform (mgc_dt_ops.inl), T = its uint16 array.  Both scans in one launch (k_dt_axis) where a tile line
+     * fits a workgroup -- ceil(tiles / 8) waves, at most 16 -- else, and with first_relabel_dt = 2 always, a forward and a backward
+     * launch of k_dt_scan.  SEED: what `in` holds; FINAL 1: the labels go to L.height, 2: uint16 to T and every label, lowered, to d_hexact. */
+    template <int AXIS, int SEED, int FINAL>
+    void dt_axis(const void* in, uint16_t* T, int c_min)
+    {
+        const MgcLattice& L = h->L;
+        const int lines = mgc_dt_lines<AXIS>(L), na = AXIS == 0 ? L.gx : (AXIS == 1 ? L.gy : L.gz);
+        void* const out = FINAL == 1 ? (void*)L.height : (void*)T;
+        int32_t* const hout = FINAL == 2 ? h->d_hexact : nullptr;
+        const int W = (na + MGC_DT_RUN - 1) / MGC_DT_RUN;
+        if (h->use_dt != 2 && W <= MGC_DT_MAXW) {
+            const int LPB = W >= 4 ? 1 : 4 / W; /* short lines share a workgroup: never a single wave */
+            hipLaunchKernelGGL((k_dt_axis<AXIS, SEED, FINAL>), dim3(grid((lines + LPB - 1) / LPB)), dim3(64 * W * LPB), 0, h->stream, L, in, out, c_min, hout, W, LPB);
+            h->launches[MGC_LAUNCH_DT_AXIS]++;
+            relabel_launches++;
+            return;
+        }
+        const dim3 g(grid((lines + 3) / 4)), blk(256);
+        hipLaunchKernelGGL((k_dt_scan<AXIS, false, SEED, 0>), g, blk, 0, h->stream, L, in, (void*)T, 0, (int32_t*)nullptr, (const uint16_t*)nullptr, (uint16_t*)nullptr, -1);
+        hipLaunchKernelGGL((k_dt_scan<AXIS, true, 0, FINAL>), g, blk, 0, h->stream, L, (const void*)T, out, c_min, hout, (const uint16_t*)nullptr, (uint16_t*)nullptr, -1);
+        h->launches[MGC_LAUNCH_DT_SCAN] += 2;
+        relabel_launches += 2;
+    }
     /* the first global relabel of a solve as a distance transform: labels, label supports and ALLINF flags as the relabel
      * passes would leave them (mgc_dt_ops.inl).  false: not applicable to this graph, run the passes. */
     bool first_relabel_dt()
@@ -2947,19 +3096,16 @@ struct HipDevT {
         h->labels_valid = true;
         const int id = time_begin(2);
         const MgcLattice& L = h->L;
-        void* const T = h->d_dt16;
+        uint16_t* const T = h->d_dt16;
         const dim3 blk(256);
         auto g = [&](int lines) { return dim3(grid((lines + 3) / 4)); };
-        hipLaunchKernelGGL((k_dt_scan<0, false, 1, 0>), g(L.gz * L.gy), blk, 0, h->stream, L, (const void*)L.rmask, T, 0, (int32_t*)nullptr, (const uint16_t*)nullptr, (uint16_t*)nullptr, -1);
-        hipLaunchKernelGGL((k_dt_scan<0, true, 0, 0>), g(L.gz * L.gy), blk, 0, h->stream, L, (const void*)T, T, 0, (int32_t*)nullptr, (const uint16_t*)nullptr, (uint16_t*)nullptr, -1);
-        hipLaunchKernelGGL((k_dt_scan<1, false, 0, 0>), g(L.gz * L.gx), blk, 0, h->stream, L, (const void*)T, T, 0, (int32_t*)nullptr, (const uint16_t*)nullptr, (uint16_t*)nullptr, -1);
-        hipLaunchKernelGGL((k_dt_scan<1, true, 0, 0>), g(L.gz * L.gx), blk, 0, h->stream, L, (const void*)T, T, 0, (int32_t*)nullptr, (const uint16_t*)nullptr, (uint16_t*)nullptr, -1);
-        hipLaunchKernelGGL((k_dt_scan<2, false, 0, 0>), g(L.gy * L.gx), blk, 0, h->stream, L, (const void*)T, T, 0, (int32_t*)nullptr, (const uint16_t*)nullptr, (uint16_t*)nullptr, -1);
-        hipLaunchKernelGGL((k_dt_scan<2, true, 0, 1>), g(L.gy * L.gx), blk, 0, h->stream, L, (const void*)T, (void*)L.height, 0, (int32_t*)nullptr, (const uint16_t*)nullptr, (uint16_t*)nullptr, -1);
+        dt_axis<0, 1, 0>((const void*)L.rmask, T, 0);
+        dt_axis<1, 0, 0>((const void*)T, T, 0);
+        dt_axis<2, 0, 1>((const void*)T, T, 0);
         hipLaunchKernelGGL(k_dt_finish, g(L.ntiles), blk, 0, h->stream, L);
         check(hipGetLastError());
         time_end(id);
-        relabel_launches += 7;
+        relabel_launches++;
         return true;
     }
     /* ---- radial labels of the flood phase (mgc_dt_ops.inl; the schedule: mgc_driver.inl) ---- */
@@ -2979,24 +3125,21 @@ struct HipDevT {
         flush_zero();
         const int id = time_begin(2);
         const MgcLattice& L = h->L;
-        void* const T = h->d_ds16;
+        uint16_t* const T = h->d_ds16;
         const dim3 blk(256);
         auto g = [&](int lines) { return dim3(grid((lines + 3) / 4)); };
         check(hipMemsetAsync(L.count + mgc_cnt_radial_c(L), 0x3f, sizeof(int32_t), h->stream)); /* MGC_HINF */
         hipLaunchKernelGGL(k_dt_cmin, g(L.ntiles), blk, 0, h->stream, L); /* C from the exact labels of the source voxels */
-        hipLaunchKernelGGL((k_dt_scan<0, false, 2, 0>), g(L.gz * L.gy), blk, 0, h->stream, L, (const void*)L.excess, T, 0, (int32_t*)nullptr, (const uint16_t*)nullptr, (uint16_t*)nullptr, -1);
-        hipLaunchKernelGGL((k_dt_scan<0, true, 0, 0>), g(L.gz * L.gy), blk, 0, h->stream, L, (const void*)T, T, 0, (int32_t*)nullptr, (const uint16_t*)nullptr, (uint16_t*)nullptr, -1);
-        hipLaunchKernelGGL((k_dt_scan<1, false, 0, 0>), g(L.gz * L.gx), blk, 0, h->stream, L, (const void*)T, T, 0, (int32_t*)nullptr, (const uint16_t*)nullptr, (uint16_t*)nullptr, -1);
-        hipLaunchKernelGGL((k_dt_scan<1, true, 0, 0>), g(L.gz * L.gx), blk, 0, h->stream, L, (const void*)T, T, 0, (int32_t*)nullptr, (const uint16_t*)nullptr, (uint16_t*)nullptr, -1);
-        hipLaunchKernelGGL((k_dt_scan<2, false, 0, 0>), g(L.gy * L.gx), blk, 0, h->stream, L, (const void*)T, T, 0, (int32_t*)nullptr, (const uint16_t*)nullptr, (uint16_t*)nullptr, -1);
+        dt_axis<0, 2, 0>((const void*)L.excess, T, 0);
+        dt_axis<1, 0, 0>((const void*)T, T, 0);
         /* ... and the labels lowered on the way, INTO THE OTHER ARRAY: the last scan reads the exact labels anyway, so it writes every label
          * (lowered or not) to the array that keeps the exact ones aside and the two trade places -- no copy of 4 bytes per voxel to keep them
          * aside here (0.2 ms at 512^3), none to bring them back (radial_restore_exact) */
-        hipLaunchKernelGGL((k_dt_scan<2, true, 0, 2>), g(L.gy * L.gx), blk, 0, h->stream, L, (const void*)T, T, c_min, h->d_hexact, (const uint16_t*)nullptr, (uint16_t*)nullptr, -1);
+        dt_axis<2, 0, 2>((const void*)T, T, c_min);
         std::swap(h->L.height, h->d_hexact); /* (kernels take the lattice by value at launch: everything from here on sees the lowered labels) */
         check(hipGetLastError());
         time_end(id);
-        relabel_launches += 8;
+        relabel_launches++;
         return true;
     }
     void radial_save_exact()
@@ -3159,16 +3302,11 @@ struct HipDevT {
         flush_zero();
         h->labels_valid = true;
         dt_span = time_begin(2);
-        const MgcLattice& L = h->L;
-        void* const T = h->dt_cur = seed == 1 ? h->d_dt16 : h->d_ds16;
-        const dim3 blk(256);
-        if (seed == 1) hipLaunchKernelGGL((k_dt_scan<0, false, 1, 0>), dt_grid(L.gz * L.gy), blk, 0, h->stream, L, (const void*)L.rmask, T, 0, (int32_t*)nullptr, (const uint16_t*)nullptr, (uint16_t*)nullptr, -1);
-        else hipLaunchKernelGGL((k_dt_scan<0, false, 2, 0>), dt_grid(L.gz * L.gy), blk, 0, h->stream, L, (const void*)L.excess, T, 0, (int32_t*)nullptr, (const uint16_t*)nullptr, (uint16_t*)nullptr, -1);
-        hipLaunchKernelGGL((k_dt_scan<0, true, 0, 0>), dt_grid(L.gz * L.gy), blk, 0, h->stream, L, (const void*)T, T, 0, (int32_t*)nullptr, (const uint16_t*)nullptr, (uint16_t*)nullptr, -1);
-        hipLaunchKernelGGL((k_dt_scan<1, false, 0, 0>), dt_grid(L.gz * L.gx), blk, 0, h->stream, L, (const void*)T, T, 0, (int32_t*)nullptr, (const uint16_t*)nullptr, (uint16_t*)nullptr, -1);
-        hipLaunchKernelGGL((k_dt_scan<1, true, 0, 0>), dt_grid(L.gz * L.gx), blk, 0, h->stream, L, (const void*)T, T, 0, (int32_t*)nullptr, (const uint16_t*)nullptr, (uint16_t*)nullptr, -1);
+        uint16_t* const T = h->dt_cur = seed == 1 ? h->d_dt16 : h->d_ds16;
+        if (seed == 1) dt_axis<0, 1, 0>((const void*)h->L.rmask, T, 0);
+        else dt_axis<0, 2, 0>((const void*)h->L.excess, T, 0);
+        dt_axis<1, 0, 0>((const void*)T, T, 0);
         check(hipGetLastError());
-        relabel_launches += 4;
     }
     /* final_kind 0: an intermediate scan; 1: the scan that writes the labels (transform towards the sink); 2: the scan that lowers the
      * labels into the other array (transform away from the source) */
@@ -3185,6 +3323,7 @@ struct HipDevT {
         else hipLaunchKernelGGL((k_dt_scan<2, true, 0, 0>), g, blk, 0, h->stream, L, (const void*)T, T, 0, (int32_t*)nullptr, cin, cout, plane);
         check(hipGetLastError());
         relabel_launches++;
+        h->launches[MGC_LAUNCH_DT_SCAN]++;
         if (bwd) { time_end(dt_span); dt_span = -1; }
     }
     void dt_finish()
@@ -3365,6 +3504,11 @@ static int mgc_solver_op_on(mgc_handle h, int op, int64_t a0, int64_t a1, int64_
     case MGC_OP_DISCHARGE: dev.discharge((int)a0, (uint32_t)a1, (int)a2, (int)a3); break;
     case MGC_OP_SUSPECT_PASS: dev.suspect_pass(); break;
     case MGC_OP_RESET_SUSPECT: dev.reset_suspect((uint32_t)a0, (int)a1); break;
+    case MGC_OP_FIRST_RELABEL: /* the first global relabel of a solve by distance transform, and nothing after it (mgc_get_heights reads the result) */
+        for (int64_t& n : h->launches) n = 0;
+        if (h->nranks > 1 || !dev.first_relabel_dt()) { h->timing = timing; return mgc_fail(h, MGC_ERR_STATE, "the distance transform does not apply to this graph (a slab, first_relabel_dt = 0, an n-link that is not residual, or labels this build already has)"); }
+        if (a0 && !dev.radial_begin((int)a1)) { h->timing = timing; return mgc_fail(h, MGC_ERR_STATE, "no radial labels on this graph"); }
+        break;
     default: h->timing = timing; return mgc_fail(h, MGC_ERR_INVALID, "unknown solver op %d", op);
     }
     if (ev_a >= 0) {
@@ -4956,7 +5100,7 @@ int mgc_set_param(mgc_handle h, const char* name, int64_t value)
     else if (!strcmp(name, "w26_raises") && value > 0) h->w26_raises = (int)value;
     else if (!strcmp(name, "w26_flags") && value >= 0) h->w26_flags = (int)value;
     else if (!strcmp(name, "wave_grid_rel") && value > 0) h->wave_grid_rel = (int)value;
-    else if (!strcmp(name, "first_relabel_dt")) h->use_dt = value != 0;
+    else if (!strcmp(name, "first_relabel_dt") && value >= 0 && value <= 2) h->use_dt = (int)value; /* 2: on, every axis as a forward + a backward launch */
     else if (!strcmp(name, "relabel_bricks")) h->use_bricks = value != 0;
     else if (!strcmp(name, "exact_sink_tiles") && value >= 0 && value <= 2) h->exact_sink_tiles = (int)value;
     else if (!strcmp(name, "sink_sweeps") && value > 0) h->sink_sweeps = (int)value;
@@ -5003,6 +5147,27 @@ int mgc_get_launch_counts(mgc_handle h, int64_t* out, int n)
 {
     if (!h || !out || n < 0) return MGC_ERR_INVALID;
     for (int k = 0; k < n && k < MGC_NLAUNCH; ++k) out[k] = h->launches[k];
+    return MGC_OK;
+}
+
+int mgc_get_heights(mgc_handle h, int which, int32_t* out)
+{
+    if (!h || !out || which < 0 || which > 1) return MGC_ERR_INVALID;
+    if (!h->built || h->nranks > 1) return mgc_fail(h, MGC_ERR_STATE, "mgc_get_heights: a built single handle");
+    const MgcLattice& L = h->L;
+    const int32_t* const src = which ? h->d_hexact : L.height;
+    if (!src) return mgc_fail(h, MGC_ERR_STATE, "mgc_get_heights: no label array is kept aside");
+    MGC_HIP(h, hipSetDevice(h->device));
+    mgc_flush_zero(h);
+    std::vector<int32_t> tiled((size_t)L.ntiles * MGC_TV);
+    MGC_HIP(h, hipMemcpyAsync(tiled.data(), src, tiled.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    MGC_HIP(h, hipStreamSynchronize(h->stream));
+    for (int64_t z = 0; z < L.dz; ++z)
+        for (int64_t y = 0; y < L.dy; ++y)
+            for (int64_t x = 0; x < L.dx; ++x) {
+                const int64_t tile = ((z >> 3) * L.gy + (y >> 3)) * L.gx + (x >> 3);
+                out[(z * L.dy + y) * L.dx + x] = tiled[(size_t)(tile * MGC_TV + (z & 7) * 64 + (y & 7) * 8 + (x & 7))];
+            }
     return MGC_OK;
 }
 

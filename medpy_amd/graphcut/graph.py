@@ -400,6 +400,19 @@ class VoxelGraph(object):
         self._call("mgc_get_stats", C.byref(st))
         return st.as_dict()
 
+    def first_relabel(self, radial=False, c_min=8):
+        """Run the first global relabel of a solve -- the distance transform towards the sink, with ``radial`` also the radial
+        labels of the flood phase (nothing below ``c_min`` hops from source to sink) -- and nothing else (MGC_OP_FIRST_RELABEL).
+        On a graph as built; MedpyHipError (ERR_STATE) where the transform does not apply.  ``heights()`` reads the result."""
+        self._call("mgc_solver_op", _lib.OP_FIRST_RELABEL, 1 if radial else 0, int(c_min), 0, 0)
+
+    def heights(self, aside=False):
+        """the distance labels, int32 array of the volume's shape (_lib.HINF: cannot reach the sink); ``aside``: the array kept
+        aside while radial labels are in use, i.e. the exact labels (mgc_get_heights)"""
+        out = numpy.empty(self._shape, dtype=numpy.int32)
+        self._call("mgc_get_heights", 1 if aside else 0, _lib.ptr(out))
+        return out
+
     def launch_counts(self):
         """{kernel form: launches} of the last solve (mgc_get_launch_counts; names: _lib.LAUNCH_KINDS)"""
         out = numpy.zeros(len(_lib.LAUNCH_KINDS), dtype=numpy.int64)

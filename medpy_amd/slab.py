@@ -385,6 +385,12 @@ class HipSlab(object):
         self._call("mgc_get_stats", self._C.byref(st))
         return st.as_dict()
 
+    def launch_counts(self):
+        """{kernel form: launches} of this slab's handle (mgc_get_launch_counts; names: _lib.LAUNCH_KINDS)"""
+        out = np.zeros(len(self._lib.LAUNCH_KINDS), dtype=np.int64)
+        self._call("mgc_get_launch_counts", self._lib.ptr(out), int(out.size))
+        return dict(zip(self._lib.LAUNCH_KINDS, out.tolist()))
+
     def validate(self):
         """this slab's part of the max-flow invariants (mgc_validate); sum the dicts over the slabs (validate_slabs)"""
         v = self._lib.Validation()
