@@ -405,6 +405,23 @@ int msg_region_sums(int device, int64_t n, const int64_t* labels, const void* va
                     double* sums, int64_t* counts);
 /* merged t-links: tr[i] = tr_cap after all add_tweights calls, flow_const = what they added to the flow (graph.h:416-425) */
 int msg_set_tweights_merged(msg_handle h, const double* tr, double flow_const);
+/* Graph::maxflow may be called again after add_tweights and goes on from the residual graph it holds (lib/maxflow/src/
+ * graph.h:129-132, 211-276).  Replaces the merged t-link of the n nodes ids[] (ids NULL: n == nodes, tr[] is the whole vector)
+ * by tr[] and the flow constant by flow_const.  Checked before the first write -- ids in range, values finite, no id twice
+ * (a list that does not ascend strictly is sorted in a copy) -- and a refused call (MGC_ERR_INVALID) leaves the handle as
+ * it was.  On a handle that holds the residual graph of a finished solve (solved, no edges added since) the change is folded
+ * into the resident excess / sink capacity of each node and the next solve is WARM: no CSR build, the push-relabel goes on
+ * from the resident preflow.  The first such call after a solve keeps that solve's labels for msg_labels_delta.  On any
+ * other handle (never solved, edges pending, last solve not converged, parameter "warm" = 0) only the t-links are stored
+ * and the next solve is cold; that is no error. */
+int msg_update_tweights(msg_handle h, int64_t n, const int64_t* ids, const double* tr, double flow_const);
+/* after warm updates and the solve that followed: ascending ids of the nodes whose label differs from the solve before the
+ * first of those updates.  *n = their number; more than cap: nothing is written.  MGC_ERR_STATE without such labels or
+ * before the solve.  Same contract as mgc_labels_delta. */
+int msg_labels_delta(msg_handle h, int64_t cap, int64_t* ids, int64_t* n);
+/* out4: {the last solve skipped the CSR build, nodes folded by the last update, labels of an earlier solve are held,
+ * cold builds on this handle so far} */
+int msg_get_warm_info(msg_handle h, int64_t* out4);
 /* GraphDouble.maxflow / what_segment / get_edge (pythongraph.h:20-21, graph.h:482-498, 561-571) */
 int msg_maxflow(msg_handle h, double* flow);
 int msg_labels(msg_handle h, uint8_t* out);

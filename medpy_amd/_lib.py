@@ -179,6 +179,9 @@ SIGNATURES = {
     "msg_add_label_edges": (_INT, [_VP, _INT, _INT, C.POINTER(_I64), _VP, _VP, _INT, _DBL]),
     "msg_region_sums": (_INT, [_INT, _I64, _VP, _VP, _INT, _INT, _I64, _VP, _VP]),
     "msg_set_tweights_merged": (_INT, [_VP, _VP, _DBL]),
+    "msg_update_tweights": (_INT, [_VP, _I64, _VP, _VP, _DBL]),
+    "msg_labels_delta": (_INT, [_VP, _I64, _VP, C.POINTER(_I64)]),
+    "msg_get_warm_info": (_INT, [_VP, _VP]),
     "msg_maxflow": (_INT, [_VP, C.POINTER(_DBL)]),
     "msg_labels": (_INT, [_VP, _VP]),
     "msg_what_segment": (_INT, [_VP, _I64, C.POINTER(_INT)]),

@@ -4481,6 +4481,26 @@ static int mgc_zero_plane(mgc_handle h, uint8_t** dst)
     return MGC_OK;
 }
 
+/* The launches of a label delta over any two byte vectors cur / prev of n entries; d_off holds n / MGC_DELTA_SEG (rounded up)
+ * + 1 counters.  out == NULL: count and scan, the total lands in d_off[nseg]; else the `total` ids are written to out.  Inside
+ * the library only (the sparse-graph solver's msg_labels_delta runs the same kernels): not part of the C ABI, not exported. */
+__attribute__((visibility("hidden"))) int64_t mgc_labels_delta_segments(int64_t n) { return (n + MGC_DELTA_SEG - 1) / MGC_DELTA_SEG; }
+
+__attribute__((visibility("hidden"))) hipError_t mgc_labels_delta_launch(hipStream_t stream, const uint8_t* cur, const uint8_t* prev, int64_t n,
+                                                                         unsigned long long* d_off, int64_t total, int64_t* out)
+{
+    const int64_t nseg = mgc_labels_delta_segments(n);
+    const int64_t wgs = (nseg + 3) / 4;
+    const unsigned grid = (unsigned)(wgs < 16384 ? wgs : 16384);
+    if (!out) {
+        hipLaunchKernelGGL(k_labels_delta_count, dim3(grid), dim3(256), 0, stream, cur, prev, n, nseg, d_off);
+        hipLaunchKernelGGL(k_labels_delta_scan, dim3(1), dim3(MGC_SCAN_THREADS), 0, stream, d_off, nseg);
+    } else {
+        hipLaunchKernelGGL(k_labels_delta_write, dim3(grid), dim3(256), 0, stream, cur, prev, n, nseg, (const unsigned long long*)d_off, total, out);
+    }
+    return hipGetLastError();
+}
+
 int mgc_edit_markers(mgc_handle h, int64_t n, const int64_t* ids, const uint8_t* ops)
 {
     if (!h) return MGC_ERR_INVALID;
@@ -4576,13 +4596,9 @@ int mgc_labels_delta(mgc_handle h, int64_t cap, int64_t* ids, int64_t* n)
     { const int rc = mgc_call_scratch(h, 0, off_bytes, &p, &own); if (rc) return rc; }
     if (own) { (void)mgc_dfree(own); return mgc_fail(h, MGC_ERR_UNSUPPORTED, "mgc_labels_delta: %lld segments do not fit the handle's scratch", (long long)nseg); } /* (cannot happen: a tile is 512 voxels, a segment 16384) */
     unsigned long long* const d_off = (unsigned long long*)p;
-    const int64_t wgs = (nseg + 3) / 4;
-    const unsigned grid = (unsigned)(wgs < 16384 ? wgs : 16384);
     float ms = 0.f, ms2 = 0.f;
     MGC_HIP(h, hipEventRecord(h->ev[2], h->stream));
-    hipLaunchKernelGGL(k_labels_delta_count, dim3(grid), dim3(256), 0, h->stream, (const uint8_t*)h->d_labels, (const uint8_t*)h->d_labels_prev, h->nvox, nseg, d_off);
-    hipLaunchKernelGGL(k_labels_delta_scan, dim3(1), dim3(MGC_SCAN_THREADS), 0, h->stream, d_off, nseg);
-    MGC_HIP(h, hipGetLastError());
+    MGC_HIP(h, mgc_labels_delta_launch(h->stream, h->d_labels, h->d_labels_prev, h->nvox, d_off, 0, nullptr));
     MGC_HIP(h, hipEventRecord(h->ev[3], h->stream));
     unsigned long long* const h_total = (unsigned long long*)(h->h_scalar + 7);
     MGC_HIP(h, hipMemcpyAsync(h_total, d_off + nseg, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
@@ -4593,11 +4609,7 @@ int mgc_labels_delta(mgc_handle h, int64_t cap, int64_t* ids, int64_t* n)
     if (total > 0 && total <= cap) {
         { const int rc = mgc_call_scratch(h, off_bytes, (size_t)total * sizeof(int64_t), &p, &own); if (rc) return rc; }
         hipError_t e = hipEventRecord(h->ev[2], h->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_labels_delta_write, dim3(grid), dim3(256), 0, h->stream, (const uint8_t*)h->d_labels, (const uint8_t*)h->d_labels_prev, h->nvox, nseg,
-                               (const unsigned long long*)d_off, total, (int64_t*)p);
-            e = hipGetLastError();
-        }
+        if (e == hipSuccess) e = mgc_labels_delta_launch(h->stream, h->d_labels, h->d_labels_prev, h->nvox, d_off, total, (int64_t*)p);
         if (e == hipSuccess) e = hipEventRecord(h->ev[3], h->stream);
         if (e == hipSuccess) e = mgc_staged_copy(h, p, ids, (size_t)total * sizeof(int64_t), false);
         else (void)hipStreamSynchronize(h->stream);

@@ -121,6 +121,18 @@ MSG_HD bool msg_relabel_relax_node(const MsgCsr& G, int64_t u)
 
 MSG_HD bool msg_active_node(const MsgCsr& G, int64_t u) { return G.excess[u] > 0.0 && G.height[u] < MSG_HINF; }
 
+/* A new merged t-link for one node of a resident preflow (msg_update_tweights).  excess - sink is the node's signed excess:
+ * what it still holds minus what it may still send to the sink; a t-link that grows by d moves it by d, whatever was pushed
+ * to the sink so far (lowering the link below that flow hands the difference back as excess).  Arcs are not touched. */
+MSG_HD void msg_fold_tlink_node(const MsgCsr& G, double* tr, int64_t u, double tr_new)
+{
+    const double x = G.excess[u] - G.sink[u];
+    const double x2 = x + (tr_new - tr[u]);
+    G.excess[u] = x2 > 0.0 ? x2 : 0.0;
+    G.sink[u] = x2 < 0.0 ? -x2 : 0.0;
+    tr[u] = tr_new;
+}
+
 /* schedule shared by the library and the simulator: Dev provides relabel_init(), relabel_pass() -> launches,
  * push(), gather(), zero_count(i), read_counts(int[4]) */
 struct MsgSolveStats {

@@ -100,7 +100,9 @@ def graph_from_labels(
     weights the ``boundary_term(graph, label_image, boundary_term_args)`` plug-in supplies (see
     :mod:`medpy_amd.graphcut.energy_label`), ``regional_term(graph, label_image, regional_term_args)`` supplies
     t-weights, and the regions under the markers are wired to the terminals with ``GCGraph.MAX``.  The region adjacency
-    graph is assembled and solved in MI355X HBM; the returned object is the stand-in for ``maxflow.GraphDouble``.
+    graph is assembled and solved in MI355X HBM; the returned object is the stand-in for ``maxflow.GraphDouble``, a
+    ``RegionGraph``: its markers can be replaced (``update_markers``) or edited by voxel lists (``edit_markers``) and
+    ``maxflow()`` then goes on from the residual graph it holds, as the reference's does (graph.h:129-132, 211-276).
 
     Raises ``AttributeError`` for a malformed label image or terms that do not take three parameters."""
     regions = numpy.asarray(label_image)
@@ -117,6 +119,7 @@ def graph_from_labels(
     boundary(graph, regions, boundary_term_args)
     graph.set_source_nodes(numpy.unique(regions[fg_mask]) - 1)
     graph.set_sink_nodes(numpy.unique(regions[bg_mask]) - 1)
+    graph.record_region_markers(regions, fg_mask, bg_mask)   # -> a RegionGraph: the markers can be edited and the cut solved again warm
     return graph.get_graph()
 
 

@@ -476,6 +476,10 @@ class SparseGraph(object):
         self._raw_pairs = set()
         self._host_arcs = {}   # GraphFloat / GraphInt: (i, j) -> [capacity of the front arc, sum of the parallel arcs behind it]
         self._host_sent = {}   # ... (i, j) with i < j -> (capacity, reverse capacity) the device holds for the pair so far
+        self._sent_tr = None   # the merged t-links (and flow constant) the device was last told: maxflow() sends what differs
+        self._sent_flow_const = None
+        self._dev_solved = False   # the device holds a finished solve of the edges sent so far: the next solve may be warm
+        self._dev_updated = False   # ... and was sent t-link updates since
 
     def update_markers(self, fg_markers, bg_markers):
         """Warm updates exist for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
@@ -547,6 +551,7 @@ class SparseGraph(object):
         rev = numpy.ascontiguousarray(rev, dtype=numpy.float64)
         self._call("msg_add_edges", i.size, _lib.ptr(i), _lib.ptr(j), _lib.ptr(cap), _lib.ptr(rev))
         self._labels = None
+        self._dev_solved = False
 
     def _add_lattice_edges(self, term, image, sigma, spacing):
         self._flush()
@@ -556,6 +561,7 @@ class SparseGraph(object):
         self._call("msg_add_lattice_edges", _lib.TERM_IDS[term], image.ndim, shp, _lib.ptr(image), _lib.DTYPE_IDS[image.dtype],
                    float(sigma) if sigma is not None else 0.0, sp)
         self._labels = None
+        self._dev_solved = False
 
     def _add_label_edges(self, term, label_image, image, param=0.0):
         self._flush()
@@ -567,6 +573,7 @@ class SparseGraph(object):
         self._call("msg_add_label_edges", _lib.LABEL_TERM_IDS[term], lab.ndim, shp, _lib.ptr(lab), _lib.ptr(image),
                    _lib.DTYPE_IDS[image.dtype], float(param))
         self._labels = None
+        self._dev_solved = False
 
     def _set_tweights_merged(self, tr, flow_const):
         self._tr = numpy.array(tr, dtype=numpy.float64)
@@ -601,6 +608,7 @@ class SparseGraph(object):
                 lib.msg_destroy(h)
             raise _lib.MedpyHipError(rc, msg)
         self._h, self._nodes = h, int(nodes)
+        self._sent_tr, self._sent_flow_const, self._dev_solved = None, None, False   # (a new handle: it was told nothing)
         lib.msg_destroy(old)
         if tail.size:
             self._add_edges(tail, head, cap, numpy.zeros(cap.size))
@@ -671,16 +679,91 @@ class SparseGraph(object):
 
     # -- GraphDouble surface
     def maxflow(self):
-        """GraphDouble.maxflow(), reference maxflow.cpp:472-604"""
+        """GraphDouble.maxflow(), reference maxflow.cpp:472-604.  Called again after ``add_tweights`` / ``update_tweights`` alone
+        it goes on from the residual graph of the last solve, as the reference's does (graph.h:129-132, 211-276): only the
+        t-links that differ from what the device was last told go down and the solve is warm (``warm_info()``).  Edges added,
+        ``reset()`` or a grown graph in between make it a solve from scratch, as does ``set_param("warm", 0)``."""
         self._flush()
         self._send_host_arcs()
         if self._tr is not None:
             tr = numpy.ascontiguousarray(self._tr, dtype=numpy.float64)
-            self._call("msg_set_tweights_merged", _lib.ptr(tr), float(self._flow_const))
+            if not self._send_changed_tweights(tr):
+                self._call("msg_set_tweights_merged", _lib.ptr(tr), float(self._flow_const))
+            self._sent_tr, self._sent_flow_const = tr.copy(), float(self._flow_const)
         flow = C.c_double(0.0)
+        self._dev_solved = self._dev_updated = False
         self._call("msg_maxflow", C.byref(flow))
+        self._dev_solved = True
         self._labels = None
         return self._out(flow.value)
+
+    def _send_changed_tweights(self, tr):
+        """the entries of ``tr`` that differ from what the device holds, through msg_update_tweights; False where the whole
+        vector has to go instead (no finished solve of these edges on the device, or values the list call refuses)"""
+        if not self._dev_solved or self._sent_tr is None or self._sent_tr.size != tr.size:
+            return False
+        ids = numpy.flatnonzero(tr != self._sent_tr).astype(numpy.int64)
+        if not ids.size and self._dev_updated and self._flow_const == self._sent_flow_const:
+            return True   # update_tweights sent it all
+        vals = numpy.ascontiguousarray(tr[ids])
+        if not (numpy.isfinite(vals).all() and numpy.isfinite(self._flow_const)):
+            return False
+        self._call("msg_update_tweights", ids.size, _lib.ptr(ids), _lib.ptr(vals), float(self._flow_const))
+        self._dev_updated = True
+        return True
+
+    # -- warm re-solves (DESIGN 10, "The sparse-graph solver")
+    def update_tweights(self, nodes, tr, flow_const=None):
+        """Replace the merged t-links of the DISTINCT node ids ``nodes`` by ``tr`` (positive: capacity from the source, negative:
+        to the sink -- ``get_trcap``'s value) and keep the residual graph: on a graph that holds a finished cut the next
+        ``maxflow()`` is a warm solve, and that cut's labels are kept on the device for ``changed_nodes()``.  The flow
+        ``maxflow()`` reports is ``flow_const`` + the capacity of the minimum cut of the graph with the merged t-links;
+        ``flow_const=None`` keeps the constant the graph has (what its ``add_tweights`` calls added up), any other value
+        replaces it.  The library checks the list before it writes (MedpyHipError, ERR_INVALID: id out of range or twice,
+        value not finite); a refused call changes nothing."""
+        ids = numpy.asarray(nodes)
+        if ids.ndim != 1 or (ids.size and ids.dtype.kind not in "iu"):
+            raise ValueError("update_tweights: node ids must be a 1-D integer array")
+        ids = numpy.ascontiguousarray(ids, dtype=numpy.int64)
+        vals = numpy.array([self._cast(v) for v in numpy.asarray(tr).reshape(-1)], dtype=numpy.float64)
+        if vals.size != ids.size:
+            raise ValueError("update_tweights: %d node ids, %d t-links" % (ids.size, vals.size))
+        fc = self._flow_const if flow_const is None else self._cast(flow_const)
+        self._flush()
+        self._send_host_arcs()
+        if self._dev_solved and self._sent_tr is not None:
+            self._call("msg_update_tweights", ids.size, _lib.ptr(ids), _lib.ptr(vals), float(fc))
+            self._sent_tr[ids] = vals
+            self._sent_flow_const = float(fc)
+            self._dev_updated = True
+        else:   # nothing to keep on the device: checked here the way the library does, sent whole by maxflow()
+            if ids.size and (ids.min() < 0 or ids.max() >= self._nodes or numpy.unique(ids).size != ids.size or not numpy.isfinite(vals).all()):
+                raise _lib.MedpyHipError(_lib.ERR_INVALID, "update_tweights: node id out of range or twice, or a t-link that is not finite")
+        if self._tr is None:
+            self._tr = numpy.zeros(self._nodes, dtype=numpy.float64)
+        self._tr[ids] = vals
+        self._flow_const = fc
+        self._labels = None
+
+    def changed_nodes(self):
+        """After t-link updates (one or several) on a solved graph and the warm ``maxflow()`` that followed: ascending int64 array
+        of the ids of the nodes whose label differs from the cut the graph held before the first of those updates.
+        MedpyHipError (ERR_STATE) when the graph holds no such earlier cut (the last solve was cold) or is not solved."""
+        n = C.c_int64(0)
+        ids = numpy.empty(1024, dtype=numpy.int64)
+        self._call("msg_labels_delta", ids.size, _lib.ptr(ids), C.byref(n))
+        if n.value > ids.size:
+            ids = numpy.empty(n.value, dtype=numpy.int64)
+            self._call("msg_labels_delta", ids.size, _lib.ptr(ids), C.byref(n))
+        return ids[:n.value].copy() if ids.size != n.value else ids
+
+    def warm_info(self):
+        """``skipped_build``: the last ``maxflow()`` went on from the resident residual graph; ``folded``: nodes whose t-link the
+        last update changed there; ``snapshot``: labels of an earlier cut are held for ``changed_nodes()``; ``cold_builds``:
+        residual graphs built from the edge list on this handle so far"""
+        out = numpy.zeros(4, dtype=numpy.int64)
+        self._call("msg_get_warm_info", _lib.ptr(out))
+        return {"skipped_build": bool(out[0]), "folded": int(out[1]), "snapshot": bool(out[2]), "cold_builds": int(out[3])}
 
     def _send_host_arcs(self):
         """GraphFloat / GraphInt: the arcs accumulated on the host go to the device, parallel arcs summed (exactly: float32
@@ -704,8 +787,27 @@ class SparseGraph(object):
             self._add_edges(numpy.array(ii, dtype=numpy.int64), numpy.array(jj, dtype=numpy.int64),
                             numpy.array(cc, dtype=numpy.float64), numpy.array(rr, dtype=numpy.float64))
 
-    def labels(self):
-        """every node at once: bool array, False where what_segment == SINK"""
+    def labels(self, out=None):
+        """every node at once: bool array, False where what_segment == SINK.
+
+        ``out``: a writeable C-contiguous bool or uint8 array of one entry per node that holds the labels of the previous cut
+        (what ``changed_nodes()`` refers to).  Only the ids of the changed nodes are read from the device and ``out`` is
+        flipped there and returned; where the graph keeps no previous cut all labels are read into ``out``.  Same meaning as
+        ``VoxelGraph.labels(out=)``."""
+        if out is not None:
+            if not (isinstance(out, numpy.ndarray) and out.shape == (self._nodes,) and out.dtype in (numpy.bool_, numpy.uint8)
+                    and out.flags.c_contiguous and out.flags.writeable):
+                raise ValueError("labels(out=...): a writeable C-contiguous bool or uint8 array of shape (%d,)" % self._nodes)
+            flat = out.view(numpy.uint8)
+            try:
+                ids = self.changed_nodes()
+            except _lib.MedpyHipError as e:
+                if e.code != _lib.ERR_STATE:
+                    raise
+                self._call("msg_labels", _lib.ptr(flat))   # (not solved: ERR_STATE again, from here)
+                return out
+            flat[ids] ^= 1
+            return out
         if self._labels is None:
             out = numpy.empty(self._nodes, dtype=numpy.uint8)
             self._call("msg_labels", _lib.ptr(out))
@@ -797,6 +899,94 @@ class GraphInt(SparseGraph):
     @staticmethod
     def _out(v):
         return int(round(v))
+
+
+def merge_tweights_into(tr, flow_const, nodes, weights_source, weights_sink):
+    """``Graph::add_tweights`` (graph.h:416-425), call by call in the order of the DISTINCT ids ``nodes``, on the merged t-links
+    ``tr`` (written in place); returns the flow constant after the calls."""
+    nodes = numpy.asarray(nodes, dtype=numpy.int64)
+    if nodes.size == 0:
+        return flow_const
+    cs = numpy.array(weights_source, dtype=numpy.float64)
+    ck = numpy.array(weights_sink, dtype=numpy.float64)
+    delta = tr[nodes]
+    cs = cs + numpy.where(delta > 0, delta, 0.0)
+    ck = ck - numpy.where(delta > 0, 0.0, delta)
+    tr[nodes] = cs - ck
+    return float(numpy.cumsum(numpy.concatenate([[flow_const], numpy.minimum(cs, ck)]))[-1])  # in call order
+
+
+def merge_region_markers(tr, flow_const, fg_nodes, bg_nodes, weight):
+    """The hard constraints on top of the t-links the terms left (generate.py:169-172, 322-338; graph.py:334-380): the nodes
+    ``fg_nodes`` get (weight, 0), then the nodes ``bg_nodes`` (0, weight), each list ascending and distinct, merged like any other
+    t-link (a node in both ends up with weight on both sides).  ``tr`` (None: no t-links so far) is not written; returns
+    ``(merged t-links, flow constant)``.  What ``GCGraph`` runs when it hands a graph to the sparse-graph solver, and what
+    ``RegionGraph`` runs again on the t-links it kept from before the markers when the markers change."""
+    fg_nodes, bg_nodes = numpy.asarray(fg_nodes, dtype=numpy.int64), numpy.asarray(bg_nodes, dtype=numpy.int64)
+    out = numpy.array(tr, dtype=numpy.float64)
+    flow_const = merge_tweights_into(out, flow_const, fg_nodes, numpy.full(fg_nodes.size, float(weight)), numpy.full(fg_nodes.size, 0.0))
+    flow_const = merge_tweights_into(out, flow_const, bg_nodes, numpy.full(bg_nodes.size, 0.0), numpy.full(bg_nodes.size, float(weight)))
+    return out, flow_const
+
+
+class RegionGraph(SparseGraph):
+    """What ``graph_from_labels`` returns: a ``SparseGraph`` whose nodes are the regions of a label image (node r - 1 = region r),
+    which remembers how its t-links came about -- the merged t-links of the terms from before the markers, and the markers as
+    voxel masks of the label image -- so that the markers can be edited and the cut solved again warm:
+    ``update_markers`` by masks, ``edit_markers`` by voxel ids, ``markers()``, ``changed_labels()``.  A region is marked while
+    at least one marked voxel lies in it."""
+
+    def _set_regions(self, label_image, fg_mask, bg_mask, tr, flow_const):
+        self._label_image = label_image   # by reference: never written
+        self._lab_flat = numpy.asarray(label_image).reshape(-1)
+        self._tr0 = numpy.zeros(self._nodes, dtype=numpy.float64) if tr is None else numpy.array(tr, dtype=numpy.float64)
+        self._flow_const0 = float(flow_const)
+        self._set_masks(fg_mask, bg_mask)
+
+    def _set_masks(self, fg_mask, bg_mask):
+        self._vox, self._cnt = [], []   # [fg, bg]: flat bool mask; marked voxels per region
+        for mask in (fg_mask, bg_mask):
+            vox = numpy.zeros(self._lab_flat.size, dtype=numpy.bool_) if mask is None else numpy.array(mask, dtype=numpy.bool_).reshape(-1)
+            self._vox.append(vox)
+            self._cnt.append(numpy.bincount(self._lab_flat[vox].astype(numpy.int64) - 1, minlength=self._nodes))
+
+    def _remerge(self):
+        self._tr, self._flow_const = merge_region_markers(self._tr0, self._flow_const0, numpy.flatnonzero(self._cnt[0]),
+                                                          numpy.flatnonzero(self._cnt[1]), float(GCGraph.MAX))
+        self._labels = None
+
+    def update_markers(self, fg_markers, bg_markers):
+        """Replace the markers (arrays of the label image's shape, non-zero = marked; None = no markers of that kind): the regions
+        under them are wired to the terminals with ``GCGraph.MAX`` on top of the terms' t-links, foreground first, as
+        ``graph_from_labels`` does.  The residual graph is kept; ``maxflow()`` sends the t-links that changed and solves warm."""
+        shape = numpy.shape(self._label_image)
+        for m, what in ((fg_markers, "foreground markers"), (bg_markers, "background markers")):
+            if m is not None and numpy.shape(m) != shape:
+                raise ValueError("%s of shape %s on a label image of shape %s" % (what, numpy.shape(m), shape))
+        self._set_masks(fg_markers, bg_markers)
+        self._remerge()
+
+    def edit_markers(self, fg=None, bg=None, erase=None):
+        """Edit the markers by lists of VOXELS of the label image (a stroke is drawn on the image, not on regions):
+        ``fg' = (fg & ~erase) | fg_ids``, ``bg' = (bg & ~erase) | bg_ids``; the arguments take the forms ``merge_marker_edits``
+        describes.  A region stays marked until its last marked voxel is erased.  Otherwise as ``update_markers``."""
+        ids, ops = merge_marker_edits(numpy.shape(self._label_image), fg, bg, erase)
+        for vox, cnt, set_bit, clear_bit in ((self._vox[0], self._cnt[0], 1, 4), (self._vox[1], self._cnt[1], 2, 8)):
+            for sel, value in (((ops & set_bit) != 0, True), ((ops & clear_bit) != 0, False)):
+                v = ids[sel]
+                v = v[vox[v] != value]   # (ids are distinct: every voxel that changes counts once)
+                vox[v] = value
+                numpy.add.at(cnt, self._lab_flat[v].astype(numpy.int64) - 1, 1 if value else -1)
+        self._remerge()
+
+    def markers(self):
+        """(fg, bg): the markers the graph holds now, bool arrays of the label image's shape"""
+        shape = numpy.shape(self._label_image)
+        return self._vox[0].reshape(shape).copy(), self._vox[1].reshape(shape).copy()
+
+    def changed_labels(self):
+        """``changed_nodes()``: the 0-based ids (node r - 1 = region r) of the regions whose label flipped"""
+        return self.changed_nodes()
 
 
 def region_sums(label_image, values, nregions, device=0):
@@ -987,6 +1177,7 @@ class GCGraph(object):
         self.__flow_const = 0.0
         self.__graph = None
         self.__lattice_shape = None  # set when the boundary image has another shape than the markers
+        self.__region_image = None   # (label image, fg mask, bg mask) of graph_from_labels
 
     # -- fast path hooks used by medpy_amd.graphcut.energy_voxel
     def record_boundary(self, term, image, sigma, spacing):
@@ -1019,13 +1210,7 @@ class GCGraph(object):
             raise ValueError("Invalid node id of {} or {}. Valid values are 0 to {}.".format(nodes.max(), nodes.min(), self.__nodes - 1))
         if self.__tr is None:
             self.__tr = numpy.zeros(self.__nodes, dtype=numpy.float64)
-        cs = numpy.array(weights_source, dtype=numpy.float64)
-        ck = numpy.array(weights_sink, dtype=numpy.float64)
-        delta = self.__tr[nodes]
-        cs = cs + numpy.where(delta > 0, delta, 0.0)
-        ck = ck - numpy.where(delta > 0, 0.0, delta)
-        self.__flow_const = float(numpy.cumsum(numpy.concatenate([[self.__flow_const], numpy.minimum(cs, ck)]))[-1])  # in call order
-        self.__tr[nodes] = cs - ck
+        self.__flow_const = merge_tweights_into(self.__tr, self.__flow_const, nodes, weights_source, weights_sink)
 
     def record_regional(self, probability_map, alpha):
         pm = numpy.asarray(probability_map)
@@ -1177,7 +1362,7 @@ class GCGraph(object):
         generate.py:159-172, 322-338) on the sparse-graph solver"""
         if self.__connectivity not in (None, 2 * len(self.__shape)):
             raise NotImplementedError("medpy_amd: the full neighbourhood exists for 1-D..3-D voxel lattices only")
-        g = SparseGraph(self.__nodes, self.__edges, device=self.__device)
+        g = (SparseGraph if self.__region_image is None else RegionGraph)(self.__nodes, self.__edges, device=self.__device)
         if self.__regional is not None:  # energy_voxel.py:61-65 in the map's dtype, then graph.py:551-552
             pm, alpha = self.__regional
             pm = numpy.asarray(pm)
@@ -1192,14 +1377,23 @@ class GCGraph(object):
             g._add_label_edges(term, lab, img, param)
         if self.__edge_i:
             g._add_edges(self.__edge_i, self.__edge_j, self.__edge_w, self.__edge_r)
-        for marks, src, snk in ((self.__fg, float(self.MAX), 0.0), (self.__bg, 0.0, float(self.MAX))):
-            if marks is not None:
-                ids = numpy.flatnonzero(numpy.asarray(marks).ravel())
-                self.merge_tweights(ids, numpy.full(ids.size, src), numpy.full(ids.size, snk))
+        if self.__region_image is not None:   # the t-links as they stand before the markers: what a marker edit merges onto again
+            g._set_regions(*self.__region_image, tr=self.__tr, flow_const=self.__flow_const)
+        fg_nodes, bg_nodes = (numpy.empty(0, dtype=numpy.int64) if m is None else numpy.flatnonzero(numpy.asarray(m).ravel())
+                              for m in (self.__fg, self.__bg))
+        if self.__tr is not None or fg_nodes.size or bg_nodes.size:
+            self.__tr, self.__flow_const = merge_region_markers(numpy.zeros(self.__nodes) if self.__tr is None else self.__tr,
+                                                                self.__flow_const, fg_nodes, bg_nodes, self.MAX)
         self.__fg = self.__bg = None
         if self.__tr is not None:
             g._set_tweights_merged(self.__tr, self.__flow_const)
         return g
+
+    def record_region_markers(self, label_image, fg_mask, bg_mask):
+        """``graph_from_labels``: the label image whose regions are the nodes, and the marker masks on it.  The graph built is
+        then a ``RegionGraph``, whose markers can be edited (the nodes under the markers still come through
+        ``set_source_nodes`` / ``set_sink_nodes``)."""
+        self.__region_image = (label_image, fg_mask, bg_mask)
 
     def get_node_count(self):
         return self.__nodes
