@@ -221,6 +221,28 @@ int mgc_set_image_range(mgc_handle h, const double* in3);
 int mgc_add_edges(mgc_handle h, int64_t n, const int64_t* i, const int64_t* j, const double* cap, const double* rev);
 int mgc_set_tweights_merged(mgc_handle h, const double* tr, double flow_const);
 
+/* Dense n-link weight arrays: the bulk form of the plug-in path, for boundary terms the caller evaluates itself (a gradient
+ * map, a learned edge probability, a directed penalty).  `offset` has ndim components in {-1,0,1} and must be a neighbour of
+ * the handle's lattice (rule and error of mgc_get_nweights_offset); `there` and `back` are C-contiguous arrays of the handle's
+ * shape, dtype MGC_F32 or MGC_F64 (f32 is widened on the device), in the layout mgc_get_nweights_offset returns: there[p] is
+ * added to the capacity of the arc p -> p + offset, back[p] to the capacity of the arc p + offset -> p.  Entries whose
+ * p + offset lies outside the volume are ignored whatever they hold.  back == NULL: `there` is used both ways.
+ *   Semantics of sum_edge (graph.h:457-480): calls accumulate per arc in call order with sequential f64 adds, so with no
+ * built-in term and one call per offset the capacity is 0.0 + w == w bit for bit.  A build applies, in this order: the
+ * boundary term's weight, then these arrays, then the batch of mgc_add_edges.  The arrays are kept on the device in a
+ * tile-major store that stays with the handle (8 * ndir bytes per voxel, allocated by the first call; a direction that is
+ * given again costs 8 bytes per voxel more, so that the adds keep their order), and the capacities as built are materialised
+ * as for explicit edges (another 8 * ndir bytes per voxel): a rebuild applies the store again, mgc_clear_nweights forgets and
+ * frees it.  Either call on a built handle makes it unbuilt, as mgc_add_edges does.
+ *   Every entry that is not ignored must be finite and >= 0 (zero: a one-way arc).  The arrays are checked on the device before
+ * the store is written: MGC_ERR_INVALID, with mgc_last_error naming the flat index and the value of the first offender, and the
+ * handle exactly as it was.  MGC_ERR_UNSUPPORTED on a slab handle.  After a call that went through, mgc_last_error holds a note
+ * of where its time went (upload_ms, check_ms, accumulate_ms).
+ *   A 6-connected graph with such arrays, no batch of explicit edges, and every arc inside the volume residual after the build
+ * starts its first solve with the distance transform, like a graph of a built-in term. */
+int mgc_add_nweights(mgc_handle h, const int* offset, const void* there, const void* back, int dtype);
+int mgc_clear_nweights(mgc_handle h);
+
 /* Runs the n-link / t-link kernels: the residual graph is now resident in HBM. */
 int mgc_build(mgc_handle h);
 

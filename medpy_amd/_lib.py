@@ -137,6 +137,8 @@ SIGNATURES = {
     "mgc_labels_delta": (_INT, [_VP, _I64, _VP, C.POINTER(_I64)]),
     "mgc_add_edges": (_INT, [_VP, _I64, _VP, _VP, _VP, _VP]),
     "mgc_set_tweights_merged": (_INT, [_VP, _VP, _DBL]),
+    "mgc_add_nweights": (_INT, [_VP, C.POINTER(_INT), _VP, _VP, _INT]),
+    "mgc_clear_nweights": (_INT, [_VP]),
     "mgc_build": (_INT, [_VP]),
     "mgc_get_nweights": (_INT, [_VP, _INT, _VP]),
     "mgc_get_tweights": (_INT, [_VP, _VP]),

@@ -30,6 +30,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <chrono>
 #include <map>
 #include <string>
 #include <mutex>
@@ -46,6 +47,7 @@
 #include "mgc_terms.h"
 #include "mgc_driver.inl"
 #include "mgc_edit_ops.inl"
+#include "mgc_dense_ops.inl"
 
 #define MGC_MARKER_MAX 65535.0              /* GCGraph.MAX, graph.py:288-291 */
 
@@ -2731,6 +2733,13 @@ struct mgc_graph {
     int64_t n_edges = 0, n_runs = 0; int64_t* d_eslot = nullptr; double* d_eval = nullptr; int64_t* d_erun = nullptr;
     bool range_set = false; double range[3] = {0, 0, 0}; /* global min / max / max|.| of the image (mgc_set_image_range) */
     bool edges_applied = false; /* the stored batch went into the last build (a new mgc_add_edges replaces it) */
+    /* dense n-link weight arrays (mgc_add_nweights, mgc_dense_ops.inl): the store in the layout of cap0, allocated by the first call; the
+       planes of their own that later arrays of a direction went to, in call order; how many arrays each direction has received; the
+       table of those planes as k_dense_apply reads it (uploaded by mgc_build) */
+    double* d_dense = nullptr;
+    std::vector<double*> dense_extra[26];
+    int dense_given[26] = {};
+    const double** d_dense_planes = nullptr;
     std::map<const void*, size_t> buf_cap; /* capacity of the buffers mgc_upload manages, keyed by the owning field */
     /* outputs / scratch */
     uint8_t* d_tsum = nullptr;   /* per tile: on which side of the cut its voxels lie (k_labels8) */
@@ -4169,9 +4178,11 @@ int mgc_destroy(mgc_handle h)
     void* ptrs[] = {L.rcap, L.cap0, L.excess, L.sink, L.height, L.rmask, L.rmask32, L.obox, L.oflags, L.list[0], L.list[1], L.list[2],
                     L.list[3], L.list[4], L.list[5], L.list[6], L.list[7], L.list[8], L.list[9], L.list[10], L.list[11], L.list[12],
                     L.list[13], L.list[14], L.list[15], L.list[16], L.list[17], L.count, L.stamp, L.rstamp, L.status, h->d_tr0, h->d_part, h->d_part2, h->d_scalar,
-                    h->d_labels, h->d_labels_prev, h->d_tflags, h->d_tsum, h->d_image, h->d_lut, h->d_prob, h->d_fg, h->d_bg, h->d_tr_in, h->d_eslot, h->d_eval, h->d_erun, L.hshadow[0], L.hshadow[1], h->d_vout, h->d_dt16, h->d_ds16, h->d_hexact, h->d_halo, h->d_xchg[0], h->d_xchg[1], h->d_xchg[2], h->d_xchg[3], h->d_cnt64, h->d_carry[0], h->d_carry[1], h->d_carry_in[0], h->d_carry_in[1]};
+                    h->d_labels, h->d_labels_prev, h->d_tflags, h->d_tsum, h->d_image, h->d_lut, h->d_prob, h->d_fg, h->d_bg, h->d_tr_in, h->d_eslot, h->d_eval, h->d_erun, h->d_dense, (void*)h->d_dense_planes, L.hshadow[0], L.hshadow[1], h->d_vout, h->d_dt16, h->d_ds16, h->d_hexact, h->d_halo, h->d_xchg[0], h->d_xchg[1], h->d_xchg[2], h->d_xchg[3], h->d_cnt64, h->d_carry[0], h->d_carry[1], h->d_carry_in[0], h->d_carry_in[1]};
     for (void* p : ptrs)
         if (p) (void)mgc_dfree(p);
+    for (auto& planes : h->dense_extra)
+        for (double* p : planes) (void)mgc_dfree(p);
     if (h->h_count) (void)hipHostFree(h->h_count);
     if (h->h_scalar) (void)hipHostFree(h->h_scalar);
     free(h->h_labels);
@@ -4726,6 +4737,143 @@ int mgc_add_edges(mgc_handle h, int64_t n, const int64_t* i, const int64_t* j, c
     return MGC_OK;
 }
 
+/* ---- dense n-link weight arrays: kernels in mgc_dense_ops.inl ---- */
+static void mgc_dense_drop(mgc_handle h)
+{
+    const int64_t plane = (int64_t)h->L.ntiles * MGC_TV * (int64_t)sizeof(double);
+    if (h->d_dense) { (void)mgc_dfree(h->d_dense); h->device_bytes -= plane * h->L.ndir; h->d_dense = nullptr; }
+    for (int d = 0; d < 26; ++d) {
+        for (double* p : h->dense_extra[d]) { (void)mgc_dfree(p); h->device_bytes -= plane; }
+        h->dense_extra[d].clear();
+        h->dense_given[d] = 0;
+    }
+}
+
+static void mgc_dense_launch(mgc_handle h, bool f32, bool check, const void* there, const void* back, const int* o, double* base_d, int64_t stride_d,
+                             double* base_r, int64_t stride_r)
+{
+    const MgcLattice& L = h->L;
+    if (check) {
+        const int64_t rows = L.dz * L.dy;
+        const int grid = (int)std::min<int64_t>((rows + 3) / 4, 4096);
+        unsigned long long* const first = (unsigned long long*)(h->d_scalar + 7);
+        if (f32) hipLaunchKernelGGL((k_dense_check<float>), dim3(grid), dim3(256), 0, h->stream, L, (const float*)there, (const float*)back, o[0], o[1], o[2], first);
+        else hipLaunchKernelGGL((k_dense_check<double>), dim3(grid), dim3(256), 0, h->stream, L, (const double*)there, (const double*)back, o[0], o[1], o[2], first);
+    } else {
+        const int64_t strips = (int64_t)L.gz * L.gy * ((L.gx + 7) / 8);
+        const int grid = (int)std::min<int64_t>(strips, 2048);
+        if (f32) hipLaunchKernelGGL((k_dense_accumulate<float>), dim3(grid), dim3(MGC_TV), 0, h->stream, L, (const float*)there, (const float*)back, o[0], o[1], o[2],
+                                    base_d, stride_d, base_r, stride_r);
+        else hipLaunchKernelGGL((k_dense_accumulate<double>), dim3(grid), dim3(MGC_TV), 0, h->stream, L, (const double*)there, (const double*)back, o[0], o[1], o[2],
+                                base_d, stride_d, base_r, stride_r);
+    }
+}
+
+int mgc_add_nweights(mgc_handle h, const int* offset, const void* there, const void* back, int dtype)
+{
+    if (!h || !offset || !there) return MGC_ERR_INVALID;
+    if (h->nranks > 1) return mgc_fail(h, MGC_ERR_UNSUPPORTED, "mgc_add_nweights: not on a slab of a multi-GPU volume");
+    if (dtype != MGC_F32 && dtype != MGC_F64) return mgc_fail(h, MGC_ERR_INVALID, "mgc_add_nweights: weights must be float32 or float64");
+    int o[3] = {0, 0, 0};
+    for (int k = 0; k < h->ndim; ++k) o[3 - h->ndim + k] = offset[k];
+    const int nz = (o[0] != 0) + (o[1] != 0) + (o[2] != 0);
+    for (int k = 0; k < 3; ++k)
+        if (o[k] < -1 || o[k] > 1) return mgc_fail(h, MGC_ERR_INVALID, "offset components must be -1, 0 or 1");
+    if (nz == 0 || (h->L.ndir == 6 && nz != 1)) return mgc_fail(h, MGC_ERR_INVALID, "offset is not a neighbour of this lattice");
+    MGC_HIP(h, hipSetDevice(h->device));
+    const MgcLattice& L = h->L;
+    int d;
+    if (L.ndir == 6) d = o[2] ? (o[2] > 0 ? 1 : 0) : (o[1] ? (o[1] > 0 ? 3 : 2) : (o[0] > 0 ? 5 : 4));
+    else { const int c = (o[0] + 1) * 9 + (o[1] + 1) * 3 + (o[2] + 1); d = c < 13 ? c : c - 1; }
+    const int dr = L.ndir == 6 ? (d ^ 1) : (25 - d);
+    const size_t bytes = (size_t)h->nvox * (dtype == MGC_F32 ? sizeof(float) : sizeof(double));
+    const int64_t plane = (int64_t)L.ntiles * MGC_TV;
+    typedef std::chrono::steady_clock Clock;
+    auto ms_since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
+    /* the arrays go up into blocks of the pool that are given back before the call returns */
+    void* tmp[2] = {nullptr, nullptr};
+    double* fresh[3] = {nullptr, nullptr, nullptr}; /* what this call allocates for the store: given back if it does not go through */
+    auto release = [&]() {
+        (void)hipStreamSynchronize(h->stream);
+        for (void* p : tmp) if (p) (void)mgc_dfree(p);
+        for (double* p : fresh) if (p) (void)mgc_dfree(p);
+    };
+    auto t0 = Clock::now();
+    hipError_t e = mgc_dmalloc(&tmp[0], bytes);
+    if (e == hipSuccess && back) e = mgc_dmalloc(&tmp[1], bytes);
+    if (e == hipSuccess) e = mgc_staged_copy(h, tmp[0], const_cast<void*>(there), bytes, true);
+    if (e == hipSuccess && back) e = mgc_staged_copy(h, tmp[1], const_cast<void*>(back), bytes, true);
+    if (e != hipSuccess) { release(); MGC_HIP(h, e); }
+    const double upload_ms = ms_since(t0);
+    /* the check, before the first write to the store */
+    t0 = Clock::now();
+    unsigned long long* const h_first = (unsigned long long*)(h->h_scalar + 7);
+    e = hipMemsetAsync(h->d_scalar + 7, 0xff, sizeof(double), h->stream);
+    if (e == hipSuccess) {
+        mgc_dense_launch(h, dtype == MGC_F32, true, tmp[0], tmp[1], o, nullptr, 0, nullptr, 0);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(h_first, h->d_scalar + 7, sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { release(); MGC_HIP(h, e); }
+    const double check_ms = ms_since(t0);
+    if (*h_first != MGC_DENSE_NONE) {
+        const int which = (int)(*h_first & 1ull);
+        const int64_t id = (int64_t)(*h_first >> 1);
+        double v = 0.0;
+        float vf = 0.f;
+        if (dtype == MGC_F32) { e = hipMemcpy(&vf, (const float*)tmp[which] + id, sizeof(float), hipMemcpyDeviceToHost); v = vf; }
+        else e = hipMemcpy(&v, (const double*)tmp[which] + id, sizeof(double), hipMemcpyDeviceToHost);
+        release();
+        MGC_HIP(h, e);
+        return mgc_fail(h, MGC_ERR_INVALID, "mgc_add_nweights: %s[%lld] = %g: capacities must be finite and >= 0", which ? "back" : "there", (long long)id, v);
+    }
+    /* where the two planes of this call go: the store proper the first time a direction is given, a plane of its own after that */
+    t0 = Clock::now();
+    if (!h->d_dense) {
+        e = mgc_dmalloc((void**)&fresh[0], (size_t)plane * L.ndir * sizeof(double));
+        if (e == hipSuccess) e = hipMemsetAsync(fresh[0], 0, (size_t)plane * L.ndir * sizeof(double), h->stream);
+    }
+    double* const store = h->d_dense ? h->d_dense : fresh[0];
+    double* base[2];
+    int64_t stride[2];
+    const int dir[2] = {d, dr};
+    for (int k = 0; k < 2 && e == hipSuccess; ++k) {
+        if (h->dense_given[dir[k]] == 0) { base[k] = store + (int64_t)dir[k] * MGC_TV; stride[k] = (int64_t)L.ndir * MGC_TV; continue; }
+        e = mgc_dmalloc((void**)&fresh[1 + k], (size_t)plane * sizeof(double));
+        if (e == hipSuccess) e = hipMemsetAsync(fresh[1 + k], 0, (size_t)plane * sizeof(double), h->stream);
+        base[k] = fresh[1 + k];
+        stride[k] = MGC_TV;
+    }
+    if (e != hipSuccess) { release(); MGC_HIP(h, e); }
+    mgc_dense_launch(h, dtype == MGC_F32, false, tmp[0], tmp[1], o, base[0], stride[0], base[1], stride[1]);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { release(); MGC_HIP(h, e); }
+    const double accumulate_ms = ms_since(t0);
+    if (fresh[0]) { h->d_dense = fresh[0]; h->device_bytes += plane * L.ndir * (int64_t)sizeof(double); fresh[0] = nullptr; }
+    for (int k = 0; k < 2; ++k) {
+        if (fresh[1 + k]) { h->dense_extra[dir[k]].push_back(fresh[1 + k]); h->device_bytes += plane * (int64_t)sizeof(double); fresh[1 + k] = nullptr; }
+        h->dense_given[dir[k]]++;
+    }
+    release();
+    h->built = h->solved = false;
+    /* no error: the note says where the time of this call went (tools/gpu_dense_nweights.py records it) */
+    (void)mgc_fail(h, MGC_OK, "mgc_add_nweights: upload_ms=%.3f check_ms=%.3f accumulate_ms=%.3f", upload_ms, check_ms, accumulate_ms);
+    return MGC_OK;
+}
+
+int mgc_clear_nweights(mgc_handle h)
+{
+    if (!h) return MGC_ERR_INVALID;
+    if (h->nranks > 1) return mgc_fail(h, MGC_ERR_UNSUPPORTED, "mgc_clear_nweights: not on a slab of a multi-GPU volume");
+    MGC_HIP(h, hipSetDevice(h->device));
+    MGC_HIP(h, hipStreamSynchronize(h->stream));
+    mgc_dense_drop(h);
+    h->built = h->solved = false;
+    return MGC_OK;
+}
+
 int mgc_build(mgc_handle h)
 {
     if (!h) return MGC_ERR_INVALID;
@@ -4769,7 +4917,7 @@ int mgc_build(mgc_handle h)
     A.lut = h->lut_n > 0 ? (const double*)h->d_lut : nullptr; A.lut_n = h->lut_n;
     A.fg = h->d_fg; A.bg = h->d_bg; A.tr_in = h->d_tr_in;
     A.tr0 = h->d_tr0; A.fpart = h->d_part; A.tflags = h->d_tflags;
-    if (h->n_edges && !L.cap0) { /* explicit edges change capacities that the image no longer determines */
+    if ((h->n_edges || h->d_dense) && !L.cap0) { /* explicit edges and dense weight arrays change capacities that the image no longer determines */
         const int rc = mgc_alloc(h, &L.cap0, (int64_t)L.ntiles * MGC_TV * L.ndir);
         if (rc) return rc;
     }
@@ -4785,6 +4933,23 @@ int mgc_build(mgc_handle h)
     MGC_HIP(h, hipGetLastError());
     mgc_sum_partials(h, (int64_t)L.ntiles, h->d_scalar);
     MGC_HIP(h, hipGetLastError());
+    /* the order is fixed: the boundary term's weight (k_build), then the dense store, then the batch of mgc_add_edges */
+    if (h->d_dense) {
+        MgcDenseLayers X{nullptr, 0};
+        for (int d = 0; d < L.ndir; ++d) X.n = std::max(X.n, (int)h->dense_extra[d].size());
+        if (X.n) {
+            std::vector<const double*> table((size_t)X.n * L.ndir, nullptr);
+            for (int d = 0; d < L.ndir; ++d)
+                for (size_t k = 0; k < h->dense_extra[d].size(); ++k) table[k * L.ndir + d] = h->dense_extra[d][k];
+            const int rc = mgc_upload(h, (void**)&h->d_dense_planes, table.data(), table.size() * sizeof(const double*));
+            if (rc) return rc;
+            X.plane = h->d_dense_planes;
+        }
+        MGC_HIP(h, hipMemsetAsync(L.count + MGC_CNT_NOT_FULL, 0, sizeof(int32_t), h->stream)); /* (what k_build counted was the graph without the store) */
+        if (L.ndir == 6) hipLaunchKernelGGL((k_dense_apply<false>), dim3(grid), dim3(MGC_TV), 0, h->stream, L, (const double*)h->d_dense, X);
+        else hipLaunchKernelGGL((k_dense_apply<true>), dim3(grid), dim3(MGC_TV), 0, h->stream, L, (const double*)h->d_dense, X);
+        MGC_HIP(h, hipGetLastError());
+    }
     if (h->n_edges) {
         hipLaunchKernelGGL(k_add_edges, dim3(1024), dim3(256), 0, h->stream, L, h->n_runs, (const int64_t*)h->d_eslot,
                            (const double*)h->d_eval, (const int64_t*)h->d_erun);
@@ -4813,7 +4978,8 @@ int mgc_build(mgc_handle h)
     /* the two build counters are read: their slots (MGC_CNT_NOT_FULL is MGC_CNT_DEFERRED during a solve) are cleared with the next
      * batch of counter clears, whichever schedule drives the solve */
     h->zero_mask |= (1u << MGC_CNT_NOT_FULL) | (1u << MGC_CNT_SINK_TILES) | (1u << MGC_CNT_WALL_TILES);
-    h->all_residual = L.ndir == 6 && A.term != MGC_TERM_NONE && h->h_count[MGC_CNT_NOT_FULL] == 0 && !h->n_edges &&
+    /* with a dense store (and no list batch) the count is k_dense_apply's, of the graph as it stands: a boundary term is not needed for it */
+    h->all_residual = L.ndir == 6 && (A.term != MGC_TERM_NONE || h->d_dense) && h->h_count[MGC_CNT_NOT_FULL] == 0 && !h->n_edges &&
                       h->gd0 + L.dy + L.dx < MGC_DT_INF - 8; /* (a slab: of ITS planes; the slab group asks every slab, MgcSlabGroup::first_relabel_dt) */
     float ms = 0.f;
     MGC_HIP(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));

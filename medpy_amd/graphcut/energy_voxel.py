@@ -17,6 +17,7 @@ __all__ = [
     "boundary_maximum_exponential", "boundary_difference_exponential",
     "boundary_maximum_division", "boundary_difference_division",
     "boundary_maximum_power", "boundary_difference_power",
+    "boundary_precomputed",
 ]
 
 
@@ -91,3 +92,23 @@ def boundary_difference_power(graph, xxx_todo_changeme8):
     (original_image, sigma, spacing) = xxx_todo_changeme8
     _need_facade(graph)
     graph.record_boundary("difference_power", original_image, sigma, spacing)
+
+
+def boundary_precomputed(graph, xxx_todo_changeme9):
+    """Boundary term from weights the caller has evaluated already (extension; no reference counterpart): a gradient-magnitude
+    map, a learned edge probability, a directed penalty.  ``weights`` is a sequence of one entry per array axis, in axis order;
+    entry k holds the weights of the pairs (p, p + e_k), either one array (symmetric) or a pair ``(there, back)`` for the arcs
+    p -> p + e_k and p + e_k -> p.  Arrays have the shape of the volume (the last slice along axis k is ignored) or the layout
+    of the reference's ``__skeleton_base`` (extent - 1 along axis k).  They reach the tile solver as whole arrays
+    (``GCGraph.set_nweights_dense``), not edge by edge."""
+    (weights,) = xxx_todo_changeme9
+    _need_facade(graph)
+    weights = list(weights)
+    ndim = len(graph.get_shape())
+    if len(weights) != ndim:
+        raise ValueError("{} weight entries for a volume of {} axes".format(len(weights), ndim))
+    for axis, w in enumerate(weights):
+        if isinstance(w, (tuple, list)) and len(w) == 2 and numpy.ndim(w[0]) == ndim:
+            graph.set_nweights_dense(axis, w[0], w[1])
+        else:
+            graph.set_nweights_dense(axis, w)

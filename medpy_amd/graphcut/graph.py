@@ -141,6 +141,56 @@ def merge_marker_edits(shape, fg=None, bg=None, erase=None):
     return ids, ops
 
 
+def pad_skeleton_weights(shape, axis, weights):
+    """The per-axis weight array of the reference's ``__skeleton_base`` (energy_voxel.py:644-658: extent - 1 along ``axis``, entry p =
+    the pair (p, p + e_axis)) as an array of the full ``shape``: the same entries, and one more slice along ``axis`` that holds
+    zeros -- the entries whose neighbour lies outside the volume, which the library ignores.  Pure host code; costs one copy of the
+    array (8 bytes read and written per voxel: ~0.2 s at 512^3), which arrays of the full shape do not pay."""
+    shape = tuple(int(v) for v in shape)
+    weights = numpy.asarray(weights)
+    want = tuple(n - 1 if k == axis else n for k, n in enumerate(shape))
+    if weights.shape != want:
+        raise ValueError("weights of shape %s for axis %d of a volume of shape %s (expected %s)" % (weights.shape, axis, shape, want))
+    out = numpy.zeros(shape, dtype=weights.dtype)
+    out[tuple(slice(0, n) for n in want)] = weights
+    return out
+
+
+def _dense_offset(offset_or_axis, ndim, connectivity):
+    """the offset of ``set_nweights_dense`` as a tuple of ndim ints in {-1, 0, 1} that is a neighbour in this connectivity"""
+    if isinstance(offset_or_axis, (int, numpy.integer)) and not isinstance(offset_or_axis, bool):
+        axis = int(offset_or_axis)
+        if axis < 0 or axis >= ndim:
+            raise ValueError("axis %d of a %d-D volume" % (axis, ndim))
+        return tuple(1 if k == axis else 0 for k in range(ndim))
+    try:
+        off = tuple(int(v) for v in offset_or_axis)
+    except TypeError:
+        raise ValueError("offset must be an axis number or a sequence of %d ints" % ndim)
+    if len(off) != ndim or any(v != w for v, w in zip(off, offset_or_axis)):
+        raise ValueError("offset %r: %d whole-number components expected" % (offset_or_axis, ndim))
+    nz = sum(1 for v in off if v != 0)
+    full = connectivity not in (None, 2 * ndim)
+    if any(v < -1 or v > 1 for v in off) or nz == 0 or (not full and nz != 1):
+        raise ValueError("offset %r is not a neighbour of the %s-neighbourhood" % (off, connectivity or 2 * ndim))
+    return off
+
+
+def _dense_array(shape, offset, w, what):
+    """one weight array of ``set_nweights_dense`` in the full shape: float32 / float64 as they are, anything else as float64"""
+    w = numpy.asarray(w)
+    if w.dtype not in (numpy.float32, numpy.float64):
+        if w.dtype.kind not in "iufb":
+            raise ValueError("%s: weights of dtype %s" % (what, w.dtype))
+        w = w.astype(numpy.float64)
+    if w.shape != tuple(shape):
+        axes = [k for k, v in enumerate(offset) if v != 0]
+        if len(axes) == 1 and offset[axes[0]] == 1 and w.shape == tuple(n - 1 if k == axes[0] else n for k, n in enumerate(shape)):
+            return pad_skeleton_weights(shape, axes[0], w)
+        raise ValueError("%s of shape %s on a graph of shape %s" % (what, w.shape, tuple(shape)))
+    return numpy.ascontiguousarray(w)
+
+
 class VoxelGraph(object):
     """What ``graph_from_voxels`` returns: the stand-in for ``maxflow.GraphDouble``.
 
@@ -302,6 +352,36 @@ class VoxelGraph(object):
     def _set_tweights_merged(self, tr, flow_const):
         tr = numpy.ascontiguousarray(tr, dtype=numpy.float64)
         self._call("mgc_set_tweights_merged", _lib.ptr(tr), float(flow_const))
+
+    def _add_nweights(self, offset, there, back=None):
+        """mgc_add_nweights: ``there[p]`` is added to the arc p -> p + offset, ``back[p]`` (None: ``there[p]``) to the arc
+        p + offset -> p; arrays of the volume's shape.  float32 / float64 go up as they are, anything else as float64."""
+        def arr(a):
+            a = numpy.asarray(a)
+            if a.dtype not in (numpy.float32, numpy.float64):
+                a = a.astype(numpy.float64)
+            return numpy.ascontiguousarray(a)
+        there = arr(there)
+        self._check_volume_shape(there, "n-link weights")
+        if back is not None:
+            back = arr(back)
+            self._check_volume_shape(back, "n-link weights (back)")
+            if back.dtype != there.dtype:
+                there, back = there.astype(numpy.float64), back.astype(numpy.float64)
+        if len(tuple(offset)) != len(self._shape):
+            raise ValueError("offset %r on a graph of %d axes" % (tuple(offset), len(self._shape)))
+        off = (C.c_int * len(self._shape))(*[int(v) for v in offset])
+        self._labels = None
+        self._call("mgc_add_nweights", off, _lib.ptr(there), None if back is None else _lib.ptr(back), _lib.DTYPE_IDS[there.dtype])
+
+    def _clear_nweights(self):
+        """mgc_clear_nweights: forget the dense weight arrays (and free their store)"""
+        self._labels = None
+        self._call("mgc_clear_nweights")
+
+    def last_note(self):
+        """the library's note on the last call that went through (mgc_add_nweights: where its time went)"""
+        return (_lib.load().mgc_last_error(self._h) or b"").decode("utf-8", "replace")
 
     def _build(self):
         self._call("mgc_build")
@@ -1173,6 +1253,7 @@ class GCGraph(object):
         self.__fg = None
         self.__bg = None
         self.__edge_i, self.__edge_j, self.__edge_w, self.__edge_r = [], [], [], []
+        self.__dense = []  # (offset, there, back or None): whole n-link weight arrays, in call order (set_nweights_dense)
         self.__tr = None  # merged explicit t-links (graph.h:416-425 applied call by call)
         self.__flow_const = 0.0
         self.__graph = None
@@ -1189,7 +1270,7 @@ class GCGraph(object):
             # isolated.  Too many ids -> the same ValueError GCGraph.set_nweight raises (graph.py:418-425).
             if image.size > self.__nodes:
                 raise ValueError("Invalid node id (node_to) of {}. Valid values are 0 to {}.".format(image.size - 1, self.__nodes - 1))
-            if self.__regional is not None or self.__tr is not None or self.__edge_i:
+            if self.__regional is not None or self.__tr is not None or self.__edge_i or self.__dense:
                 raise NotImplementedError("medpy_amd: a boundary image of another shape cannot be combined with other terms")
             self.__lattice_shape = image.shape
         if self.__boundary is not None:
@@ -1285,6 +1366,30 @@ class GCGraph(object):
         self.__edge_w.append(float(weight_there))
         self.__edge_r.append(float(weight_back))
 
+    def set_nweights_dense(self, offset_or_axis, weight_there, weight_back=None):
+        """Whole n-link weight arrays at once: the call a plug-in boundary term makes instead of one ``set_nweight`` per edge
+        (extension; the reference has no bulk form).  ``offset_or_axis``: a lattice offset (one component in {-1, 0, 1} per array
+        axis, a neighbour in the connectivity of the graph) or an ``int``, the forward unit offset of that axis.
+        ``weight_there[p]`` is added to the arc p -> p + offset, ``weight_back[p]`` (None: symmetric) to the arc p + offset -> p,
+        with the semantics of ``set_nweight`` / ``sum_edge``: repeated calls accumulate in call order.  Arrays have the shape of
+        the volume (entries whose neighbour lies outside are ignored) or, for the forward offset of an axis, the layout of the
+        reference's ``__skeleton_base`` (extent - 1 along that axis), which costs a padding copy on the host
+        (``pad_skeleton_weights``).  Weights must be finite and >= 0 -- zero is allowed here, for one-way arcs -- which the
+        library checks on the device when the graph is built (``MedpyHipError``).  The arrays reach the graph after the built-in
+        boundary term and before the edges of ``set_nweight``.  ValueError for a bad offset, shape or dtype, before anything is
+        recorded; NotImplementedError on graphs the sparse-graph solver takes (no lattice shape, more than 3 axes, a boundary
+        image of another shape, an explicit edge between voxels that are not neighbours)."""
+        if self.__general or self.__lattice_shape is not None:
+            raise NotImplementedError("medpy_amd: dense n-link weight arrays need a 1-D..3-D voxel lattice on the tile solver")
+        off = _dense_offset(offset_or_axis, len(self.__shape), self.__connectivity)
+        there = _dense_array(self.__shape, off, weight_there, "weight_there")
+        back = None if weight_back is None else _dense_array(self.__shape, off, weight_back, "weight_back")
+        if back is not None and numpy.shape(weight_back) != numpy.shape(weight_there):
+            raise ValueError("weight_there of shape %s and weight_back of shape %s" % (numpy.shape(weight_there), numpy.shape(weight_back)))
+        if self.__graph is not None:
+            raise NotImplementedError("medpy_amd: the graph is built already (warm updates of the dense weights are not implemented)")
+        self.__dense.append((off, there, back))
+
     def set_nweights(self, nweights):
         for edge, weight in list(nweights.items()):
             self.set_nweight(edge[0], edge[1], weight[0], weight[1])
@@ -1336,6 +1441,8 @@ class GCGraph(object):
         if self.__graph is None and not self.__general and self.__edge_i and len(self.__shape or ()) <= 3 \
                 and not self.__edges_join_lattice_neighbours():
             self.__general = True  # a plug-in term added an edge between voxels that are not neighbours
+        if self.__graph is None and self.__dense and (self.__general or self.__lattice_shape is not None):
+            raise NotImplementedError("medpy_amd: dense n-link weight arrays on a graph that goes to the sparse-graph solver")
         if self.__graph is None and self.__general:
             self.__graph = self.__sparse_graph()
         if self.__graph is None and self.__lattice_shape is not None:
@@ -1351,6 +1458,8 @@ class GCGraph(object):
                 g._set_tweights_merged(self.__tr, self.__flow_const)
             if self.__fg is not None or self.__bg is not None:
                 g._set_markers(None if self.__fg is None else self.__fg, None if self.__bg is None else self.__bg)
+            for off, there, back in self.__dense:   # (after the boundary term, before the explicit edges: the order mgc_build applies them in)
+                g._add_nweights(off, there, back)
             if self.__edge_i:
                 g._add_edges(self.__edge_i, self.__edge_j, self.__edge_w, self.__edge_r)
             g._build()
@@ -1394,6 +1503,10 @@ class GCGraph(object):
         then a ``RegionGraph``, whose markers can be edited (the nodes under the markers still come through
         ``set_source_nodes`` / ``set_sink_nodes``)."""
         self.__region_image = (label_image, fg_mask, bg_mask)
+
+    def get_shape(self):
+        """the lattice shape the node ids refer to (``(nodes,)`` for a graph without one)"""
+        return self.__shape
 
     def get_node_count(self):
         return self.__nodes
