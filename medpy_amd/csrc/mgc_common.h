@@ -70,7 +70,9 @@
 #define MGC26_CNT_RADIAL_C 26
 #define MGC26_CNT_SOURCE_OPEN 27
 #define MGC_CNT_CHANGED 21     /* suspect-closure pass changed something */
-#define MGC_CNT_FILTER 22      /* length of the scratch list the tile filters fill (absorb / relabel seeding / suspect reset) */
+#define MGC_CNT_CHANGED_PASS 16 /* .. 19 (6-neighbourhood, single handle) one word per closure pass of a stretch between two looks: the schedule asks
+                                   whether the LAST pass changed something (HipDevT::suspect_pass, read_counts) */
+#define MGC_CNT_FILTER 22     /* length of the scratch list the tile filters fill (absorb / relabel seeding / suspect reset) */
 #define MGC_CNT_FILTER_ACT 23  /* ... of the activation filter */
 /* the filters alternate between two slots each: the kernel that consumes one list clears the slot the next filter will count
  * into (no launch in between just to clear a word) */

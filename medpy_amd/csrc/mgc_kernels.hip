@@ -834,6 +834,18 @@ __global__ void k_zero_counts(MgcLattice L, uint32_t mask)
     if (sh < L.nshard) *mgc_counter(L, c, sh) = 0;
 }
 
+/* A look at the counters without a copy engine and a stream drain: ONE wave copies the n words of the counter block into
+ * host memory the device has mapped (fine-grained, so the stores go out past the L2) and follows them with the sequence number
+ * of this look, released at system scope.  The host polls that word (HipDevT::read_counts).  All stores are this wave's own, so
+ * the wait of the release covers them; the explicit wait stands because the fence's own has been seen to go missing. */
+__global__ __launch_bounds__(64) void k_look(const int32_t* count, int32_t* out, int n, uint32_t seq)
+{
+    for (int i = (int)threadIdx.x; i < n; i += 64) out[i] = count[i];
+    __threadfence_system();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (threadIdx.x == 0) __hip_atomic_store((uint32_t*)(out + n), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 __global__ void k_status_or(MgcLattice L, uint32_t bits, uint32_t clear)
 {
     const int tile = blockIdx.x * blockDim.x + threadIdx.x;
@@ -845,7 +857,7 @@ __global__ void k_status_or(MgcLattice L, uint32_t bits, uint32_t clear)
  * only ever get set, so racing with the neighbour bricks is benign: what they add is picked up by the next pass).  The
  * closure then advances a brick per launch instead of a tile per launch: ~30 launches per 512^3 step instead of 200. */
 template <bool FULL> /* FULL: 26 supporting neighbour tiles (mgc26_suspect_tile) */
-__global__ __launch_bounds__(MGC_TV) void k_suspect_pass(MgcLattice L)
+__global__ __launch_bounds__(MGC_TV) void k_suspect_pass(MgcLattice L, int changed) /* changed: the counter word that says "this launch made a tile suspect" */
 {
     const int bxn = (L.gx + 7) / 8, byn = (L.gy + 7) / 8, bzn = (L.gz + 7) / 8;
     const int t = threadIdx.x;
@@ -862,7 +874,7 @@ __global__ __launch_bounds__(MGC_TV) void k_suspect_pass(MgcLattice L)
             if (!__syncthreads_or(ch)) break;
         }
     }
-    if (any) L.count[MGC_CNT_CHANGED] = 1;
+    if (any) L.count[changed] = 1;
 }
 
 template <bool FULL>
@@ -887,13 +899,26 @@ __global__ __launch_bounds__(MGC_TV) void k_reset_suspect(MgcLattice L, uint32_t
             L.height[(int64_t)sel[i] * MGC_TV + threadIdx.x] = MGC_HINF;
             if (threadIdx.x < MGC_TF) mgc_shadow_reset(L, sel[i], (int)threadIdx.x);
         }
+        /* 6-neighbourhood, passes over tiles: only a tile a label can come from is queued (mgc_reset_seeds_tile, the rule of
+         * mgc_reset_suspect_tile).  After the flood the suspect region is a solid ball of tens of thousands of tiles; all but
+         * its rim and the tiles with a sink link would relax INF against INF on the first pass, and the label wave wakes them
+         * when it arrives.  The suspect flags are complete when this kernel starts, and a tile's flags are retired by the ONE
+         * status store below: a neighbour that another lane or workgroup resets in this launch shows SUSPECT before that store
+         * and ALLINF after it, "no source" on either side, so the predicate does not depend on the order of the resets.
+         * The tiles left out still count as relabel visits (count[9]): the schedule weighs a relabel's visits against the
+         * discharges before it (mgc_solve, adaptive_rounds), and its thresholds were measured with one visit per reset tile. */
+        bool left_out = false;
         if ((int)threadIdx.x < n) {
             const int tile = sel[threadIdx.x];
-            L.status[tile] = (L.status[tile] & ~(MGC_ST_SUSPECT | MGC_ST_DIRTY | MGC_ST_SETTLED | (FULL ? MGC26_ST_DEP_MASK : (63u << MGC_ST_DEP_SHIFT)))) | MGC_ST_ALLINF;
+            const uint32_t st = L.status[tile];
+            const bool seeds = FULL || bricks || mgc_reset_seeds_tile(L, tile, st);
+            L.status[tile] = (st & ~(MGC_ST_SUSPECT | MGC_ST_DIRTY | MGC_ST_SETTLED | (FULL ? MGC26_ST_DEP_MASK : (63u << MGC_ST_DEP_SHIFT)))) | MGC_ST_ALLINF;
             if (bricks) mgc_enqueue_brick(x, L, list, epoch, mgc_brick_of_tile(L, tile)); /* the passes of this relabel run over bricks (k_relabel_b) */
-            else mgc_enqueue(x, L, list, L.rstamp, epoch, tile);
+            else if (seeds) mgc_enqueue(x, L, list, L.rstamp, epoch, tile);
+            left_out = !seeds;
         }
-        __syncthreads();
+        const int nleft = __syncthreads_count(left_out);
+        if (!FULL && threadIdx.x == 0 && nleft) atomicAdd(&L.count[9], nleft);
     }
 }
 
@@ -2746,6 +2771,9 @@ struct mgc_graph {
     uint8_t* d_tflags = nullptr; /* per tile: which signs of t-link k_build saw (MgcBuildArgs::tflags) */
     double* d_tr0 = nullptr; double* d_part = nullptr; double* d_part2 = nullptr; double* d_scalar = nullptr; uint8_t* d_labels = nullptr;
     int32_t* h_count = nullptr; /* pinned */
+    int32_t* h_look = nullptr;  /* pinned and mapped into the device: the counter block as k_look last wrote it, then the sequence number of that look */
+    int32_t* d_look = nullptr;  /* ... its device address */
+    uint32_t look_seq = 0;      /* number of the last look asked for (HipDevT::read_counts) */
     double* h_scalar = nullptr; /* pinned */
     uint8_t* h_labels = nullptr; bool labels_on_host = false;
     /* mgc_edit_markers: the labels of the solve the handle held when the first list edit since then arrived (C order, one byte per
@@ -2823,8 +2851,12 @@ struct mgc_graph {
     int filt[2] = {0, 0};   /* which slot of a filter's pair is in use next (HipDevT::fslot) */
     int pending_zero = -1; /* list counter the schedule asked to clear right after a discharge: the next discharge kernel clears
                               it (it neither reads nor appends to that list), any other operation flushes it with a memset first */
-    int use_filters = 3; /* bit0 absorb, bit1 activate, bit2 reset-suspect go through the tile-level filter.  Bit2 is off:
-                            measured on MI355X it doubles the number of global relabels (cause not understood yet) */
+    int use_filters = 3; /* bit0 absorb, bit1 activate, bit2 reset-suspect go through the tile-level filter.  Bit2 is off.
+                            Its reset (k_reset_suspect_list) queues only the tiles a label can come from and so reports fewer relabel
+                            visits to the schedule, which weighs them against the discharges (mgc_solve, adaptive_rounds); k_reset_suspect
+                            seeds the same way but counts the tiles it leaves out.  The doubled number of global relabels once seen with
+                            bit 2 did not come back when it was looked for (profiles/relabel_trim.jsonl: weak contrast 512^3 9 relabels /
+                            240 phases either way, CT-like 8 / 192, 11 % fewer visits) -- but bit 2 is 0.3 - 0.8 ms slower there */
     mgc_stats stats{};
     int64_t device_bytes = 0;
     std::string err;
@@ -2999,8 +3031,22 @@ struct HipDevT {
         }
         h->zero_mask = 0;
     }
+    /* The suspect closure is at its fixpoint when ONE pass changes nothing: that launch evaluated every tile against flags nobody
+     * set meanwhile.  One word for the whole stretch between two looks can only say "some pass changed something", and the
+     * schedule then pays a second stretch to learn that the first had already ended on a quiet pass.  So (6-neighbourhood,
+     * single handle) pass k of a stretch reports into a word of its own, MGC_CNT_CHANGED_PASS + k, the words are cleared with
+     * MGC_CNT_CHANGED at the start of the stretch, and read_counts hands the schedule the word of the stretch's last pass in
+     * MGC_CNT_CHANGED.  A slab keeps the one word: the closure of a slab group also crosses borders in exchange(2, ...), which
+     * can bring in flags behind the last pass.  So does a pass launched on its own (mgc_solver_op). */
+    int closure_pass = -1; /* passes of the stretch so far, or -1: no stretch open */
+    int closure_word = MGC_CNT_CHANGED;
+    bool closure_words() const { return !FULL && h->nranks == 1; }
     void zero_count(int i)
     {
+        if (i == MGC_CNT_CHANGED && closure_words()) {
+            closure_pass = 0;
+            h->zero_mask |= 15u << MGC_CNT_CHANGED_PASS;
+        }
         if (i == last_discharged) { flush_zero(); h->pending_zero = i; last_discharged = -1; return; }
         if (h->pending_zero >= 0) { h->zero_mask |= 1u << h->pending_zero; h->pending_zero = -1; }
         h->zero_mask |= 1u << i;
@@ -3008,10 +3054,34 @@ struct HipDevT {
     void read_counts(int* out)
     {
         flush_zero();
-        check(hipMemcpyAsync(h->h_count, h->L.count, MGC_NCOUNT * (1 + MGC_NSHARD) * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        check(hipStreamSynchronize(h->stream));
+        const int nw = MGC_NCOUNT * (1 + MGC_NSHARD);
+        if (h->d_look && h->nranks == 1) {
+            /* A copy D2H and a stream drain left the device idle for 17 - 59 us around each of the ~20 looks of a step.  Instead a
+             * one-wave kernel writes the block and then a sequence number into mapped host memory (k_look) and the host polls
+             * the number: one buffer per handle, a sequence that only grows, never two looks in flight.  What does not arrive
+             * in time -- a stretch of long launches, a stall, a fault -- ends in the stream drain it always ended in. */
+            const uint32_t seq = ++h->look_seq;
+            hipLaunchKernelGGL(k_look, dim3(1), dim3(64), 0, h->stream, (const int32_t*)h->L.count, h->d_look, nw, seq);
+            check(hipGetLastError());
+            const uint32_t* word = (const uint32_t*)(h->h_look + nw);
+            bool seen = false;
+            const auto t0 = std::chrono::steady_clock::now();
+            for (uint32_t spin = 1; !(seen = __atomic_load_n(word, __ATOMIC_ACQUIRE) == seq); ++spin) {
+#if !defined(__HIP_DEVICE_COMPILE__) && (defined(__x86_64__) || defined(__i386__))
+                __builtin_ia32_pause();
+#endif
+                if ((spin & 255u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(50)) break;
+            }
+            if (!seen) check(hipStreamSynchronize(h->stream));
+            memcpy(h->h_count, h->h_look, nw * sizeof(int32_t));
+        } else {
+            check(hipMemcpyAsync(h->h_count, h->L.count, nw * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+            check(hipStreamSynchronize(h->stream));
+        }
         mgc_fold_counts(h);
         memcpy(out, h->h_count, MGC_NCOUNT * sizeof(int32_t));
+        if (closure_pass > 0) out[MGC_CNT_CHANGED] = out[closure_word]; /* the word of the stretch's last pass (see zero_count) */
+        closure_pass = -1;
         readbacks++;
         if (!FULL) { /* how long are the discharge lists at the moment?  (picks the form of the discharge kernel) */
             int m = out[6] / 2; /* tiles the last activation found, two colours */
@@ -3193,7 +3263,11 @@ struct HipDevT {
     {
         flush_zero();
         const int nb = ((h->L.gx + 7) / 8) * ((h->L.gy + 7) / 8) * ((h->L.gz + 7) / 8);
-        hipLaunchKernelGGL(k_suspect_pass<FULL>, dim3(nb < 4096 ? nb : 4096), dim3(MGC_TV), 0, h->stream, h->L);
+        if (closure_pass >= 0) { /* (passes beyond the fourth of a stretch share the last word: "one of them changed something", the safe side) */
+            closure_word = MGC_CNT_CHANGED_PASS + (closure_pass < 3 ? closure_pass : 3);
+            closure_pass++;
+        }
+        hipLaunchKernelGGL(k_suspect_pass<FULL>, dim3(nb < 4096 ? nb : 4096), dim3(MGC_TV), 0, h->stream, h->L, closure_pass >= 0 ? closure_word : MGC_CNT_CHANGED);
         check(hipGetLastError());
     }
     void reset_suspect(uint32_t epoch, int list)
@@ -3728,6 +3802,9 @@ static int mgc_create_impl(int ndim, const int64_t* shape, int connectivity, int
     if ((rc = mgc_alloc(h, &h->d_labels, n))) return rc;
     MGC_HIP(h, hipHostMalloc((void**)&h->h_count, MGC_NCOUNT * (1 + MGC_NSHARD) * sizeof(int32_t), hipHostMallocDefault));
     MGC_HIP(h, hipHostMalloc((void**)&h->h_scalar, 8 * sizeof(double), hipHostMallocDefault));
+    MGC_HIP(h, hipHostMalloc((void**)&h->h_look, (MGC_NCOUNT * (1 + MGC_NSHARD) + 1) * sizeof(int32_t), hipHostMallocMapped | hipHostMallocCoherent));
+    memset(h->h_look, 0, (MGC_NCOUNT * (1 + MGC_NSHARD) + 1) * sizeof(int32_t));
+    MGC_HIP(h, hipHostGetDevicePointer((void**)&h->d_look, h->h_look, 0));
     MGC_HIP(h, hipMemsetAsync(L.count, 0, MGC_NCOUNT * (1 + MGC_NSHARD) * sizeof(int32_t), h->stream));
     MGC_HIP(h, hipStreamSynchronize(h->stream));
     if (const char* wv = getenv("MEDPY_HIP_WAVE")) { h->wave_kernels = atoi(wv); h->wave_set = true; } /* development aid: A/B the kernel forms */
@@ -4185,6 +4262,7 @@ int mgc_destroy(mgc_handle h)
         for (double* p : planes) (void)mgc_dfree(p);
     if (h->h_count) (void)hipHostFree(h->h_count);
     if (h->h_scalar) (void)hipHostFree(h->h_scalar);
+    if (h->h_look) (void)hipHostFree(h->h_look);
     free(h->h_labels);
     for (int i = 0; i < 4; ++i)
         if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);

@@ -15,7 +15,9 @@ build)
     cp -r $ROOT/medpy_amd/csrc $W/medpy_amd/; cp $ROOT/include/medpy_hip.h $W/include/
     FLAGS=()
     for a in "$@"; do
-        if [ -f "$a" ]; then P=$(readlink -f "$a"); (cd $W && grep -v '^#' "$P" | git apply --include='medpy_amd/csrc/*' -) || exit 1; else FLAGS+=("$a"); fi
+        # (GIT_CEILING_DIRECTORIES: inside the repository `git apply` takes the scratch copy for a subdirectory of the work tree,
+        #  skips every path of the patch as lying outside it and returns 0 -- the "variant" is then the tree itself)
+        if [ -f "$a" ]; then P=$(readlink -f "$a"); (cd $W && grep -v '^#' "$P" | GIT_CEILING_DIRECTORIES=$ROOT/build git apply --include='medpy_amd/csrc/*' -) || exit 1; else FLAGS+=("$a"); fi
     done
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared -ldl "${FLAGS[@]}" \
         $W/medpy_amd/csrc/mgc_kernels.hip $W/medpy_amd/csrc/msg_sparse.hip -o $ROOT/build/lib_$NAME.so || exit 1
