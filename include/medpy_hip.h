@@ -197,6 +197,28 @@ int mgc_edit_markers(mgc_handle h, int64_t n, const int64_t* ids, const uint8_t*
 int mgc_get_markers(mgc_handle h, uint8_t* fg, uint8_t* bg);
 int mgc_labels_delta(mgc_handle h, int64_t cap, int64_t* ids, int64_t* n);
 
+/* WARM UPDATE OF THE BOUNDARY TERM: the n-link side of the interactive loop (a cut leaks, sigma comes down, the graph is cut
+ * again; DESIGN 10, "The boundary term").  Arguments as for mgc_set_boundary; image == NULL keeps the resident image and its
+ * dtype (another sigma, term or spacing: nothing is uploaded), otherwise the new image goes up next to the old one, which is
+ * released after the update.  The capacities as built are a pure function of the resident image, so one kernel evaluates every
+ * arc's capacity under the old and under the new arguments and folds the change into the residual graph: flow that no longer
+ * fits an arc goes back to its tail as excess and is taken from its head as residual sink capacity.  The next mgc_maxflow is a
+ * warm solve; its labels, flow and mgc_validate are those of mgc_set_boundary + mgc_build + mgc_maxflow of the new arguments.  The
+ * *_linear terms measure the range of a new image again.
+ *   mgc_update_boundary_lut hands over the table of the NEW arguments (mgc_set_boundary_lut) and is called BEFORE the
+ * mgc_update_boundary it belongs to, which consumes it: the table the graph was built with stays readable until the update has
+ * run.  Without it the new term is evaluated without a table.  MGC_ERR_STATE from mgc_update_boundary if the new term has none.
+ *   States as for mgc_update_markers (MGC_ERR_STATE before mgc_build, after a solve that did not converge, on a slab handle);
+ * MGC_ERR_UNSUPPORTED on a handle whose capacities the image does not determine (explicit edges, dense weight arrays), on a
+ * handle built without a boundary term, and for term == MGC_TERM_NONE.  A refused call leaves the handle as it was.  If the
+ * handle holds a finished solve its labels are put aside as by mgc_edit_markers: mgc_labels_delta after the next mgc_maxflow
+ * reports what the new arguments flipped.
+ *   mgc_get_boundary_update_info: of the last update, out4 = {arcs whose capacity changed, arcs whose flow no longer fitted,
+ * voxels whose excess or residual sink link changed, tiles that gained a t-link flag}. */
+int mgc_update_boundary(mgc_handle h, int term, const void* image, int dtype, double sigma, const double* spacing);
+int mgc_update_boundary_lut(mgc_handle h, const double* table, int64_t n);
+int mgc_get_boundary_update_info(mgc_handle h, int64_t* out4);
+
 /* After mgc_maxflow (or the slab driver's last step): see mgc_validation.  Also works on a graph whose solve was cut
  * short (MGC_ERR_NOT_CONVERGED): it then reports the excess that is still active.  MGC_ERR_STATE before the first solve
  * step of a build: the distance labels it reads do not exist yet. */

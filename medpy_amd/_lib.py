@@ -135,6 +135,9 @@ SIGNATURES = {
     "mgc_edit_markers": (_INT, [_VP, _I64, _VP, _VP]),
     "mgc_get_markers": (_INT, [_VP, _VP, _VP]),
     "mgc_labels_delta": (_INT, [_VP, _I64, _VP, C.POINTER(_I64)]),
+    "mgc_update_boundary": (_INT, [_VP, _INT, _VP, _INT, _DBL, C.POINTER(_DBL)]),
+    "mgc_update_boundary_lut": (_INT, [_VP, _VP, _I64]),
+    "mgc_get_boundary_update_info": (_INT, [_VP, _VP]),
     "mgc_add_edges": (_INT, [_VP, _I64, _VP, _VP, _VP, _VP]),
     "mgc_set_tweights_merged": (_INT, [_VP, _VP, _DBL]),
     "mgc_add_nweights": (_INT, [_VP, C.POINTER(_INT), _VP, _VP, _INT]),

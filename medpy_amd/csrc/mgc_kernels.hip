@@ -2058,6 +2058,8 @@ __global__ __launch_bounds__(MGC_TV) void k_update_tlinks(MgcLattice L, MgcBuild
     if (!FULL && t == 0 && flagged_sink) atomicAdd(&L.count[MGC_CNT_SINK_TILES], flagged_sink);
 }
 
+#include "mgc_nlink_ops.inl"
+
 /* ======================================================================================
  * read-out
  * ==================================================================================== */
@@ -2749,6 +2751,8 @@ struct mgc_graph {
     int has_spacing = 0;
     void* d_prob = nullptr; int prob_dtype = 0; double alpha = 0;
     void* d_lut = nullptr; int lut_n = 0; /* mgc_set_boundary_lut: the boundary function by table (doubles) */
+    void* d_lut_new = nullptr; int lut_new_n = 0; /* mgc_update_boundary_lut: the table of the NEW arguments, waiting for mgc_update_boundary (the old one is read by the fold) */
+    MgcFoldCounts fold_counts{}; /* of the last mgc_update_boundary (mgc_get_boundary_update_info) */
     uint8_t* d_fg = nullptr; uint8_t* d_bg = nullptr;
     double* d_tr_in = nullptr; double flow_const_in = 0;
     /* pending explicit edges (host copy kept until build) */
@@ -4255,7 +4259,7 @@ int mgc_destroy(mgc_handle h)
     void* ptrs[] = {L.rcap, L.cap0, L.excess, L.sink, L.height, L.rmask, L.rmask32, L.obox, L.oflags, L.list[0], L.list[1], L.list[2],
                     L.list[3], L.list[4], L.list[5], L.list[6], L.list[7], L.list[8], L.list[9], L.list[10], L.list[11], L.list[12],
                     L.list[13], L.list[14], L.list[15], L.list[16], L.list[17], L.count, L.stamp, L.rstamp, L.status, h->d_tr0, h->d_part, h->d_part2, h->d_scalar,
-                    h->d_labels, h->d_labels_prev, h->d_tflags, h->d_tsum, h->d_image, h->d_lut, h->d_prob, h->d_fg, h->d_bg, h->d_tr_in, h->d_eslot, h->d_eval, h->d_erun, h->d_dense, (void*)h->d_dense_planes, L.hshadow[0], L.hshadow[1], h->d_vout, h->d_dt16, h->d_ds16, h->d_hexact, h->d_halo, h->d_xchg[0], h->d_xchg[1], h->d_xchg[2], h->d_xchg[3], h->d_cnt64, h->d_carry[0], h->d_carry[1], h->d_carry_in[0], h->d_carry_in[1]};
+                    h->d_labels, h->d_labels_prev, h->d_tflags, h->d_tsum, h->d_image, h->d_lut, h->d_lut_new, h->d_prob, h->d_fg, h->d_bg, h->d_tr_in, h->d_eslot, h->d_eval, h->d_erun, h->d_dense, (void*)h->d_dense_planes, L.hshadow[0], L.hshadow[1], h->d_vout, h->d_dt16, h->d_ds16, h->d_hexact, h->d_halo, h->d_xchg[0], h->d_xchg[1], h->d_xchg[2], h->d_xchg[3], h->d_cnt64, h->d_carry[0], h->d_carry[1], h->d_carry_in[0], h->d_carry_in[1]};
     for (void* p : ptrs)
         if (p) (void)mgc_dfree(p);
     for (auto& planes : h->dense_extra)
@@ -4952,16 +4956,10 @@ int mgc_clear_nweights(mgc_handle h)
     return MGC_OK;
 }
 
-int mgc_build(mgc_handle h)
+/* the boundary term's part of MgcBuildArgs from what the handle holds now: image, term, sigma, spacing, table (mgc_build, mgc_update_boundary) */
+static int mgc_boundary_args(mgc_handle h, MgcBuildArgs& A)
 {
-    if (!h) return MGC_ERR_INVALID;
-    MGC_HIP(h, hipSetDevice(h->device));
-    MgcRange range_("mgc_build");
-    MgcLattice& L = h->L;
-    MgcBuildArgs A{};
-    h->has_prev = false; /* (the snapshot of mgc_edit_markers belongs to the build it was taken in) */
     A.image = h->d_image; A.img_dtype = h->img_dtype; A.term = h->d_image ? h->term : MGC_TERM_NONE;
-    MGC_HIP(h, hipEventRecord(h->ev[0], h->stream));
     A.p0 = h->sigma;
     if (A.term == MGC_TERM_DIFFERENCE_EXPONENTIAL || A.term == MGC_TERM_MAXIMUM_EXPONENTIAL) A.p0 = pow(h->sigma, 2); /* math.pow(sigma, 2) */
     if (A.term == MGC_TERM_DIFFERENCE_LINEAR || A.term == MGC_TERM_MAXIMUM_LINEAR) {
@@ -4990,9 +4988,23 @@ int mgc_build(mgc_handle h)
         for (int k = 3 - h->ndim; k < 3; ++k) acc += (off[k] * h->spacing[k]) * (off[k] * h->spacing[k]);
         A.div26[d] = sqrt(acc);
     }
+    A.lut = h->lut_n > 0 ? (const double*)h->d_lut : nullptr; A.lut_n = h->lut_n;
+    return MGC_OK;
+}
+
+int mgc_build(mgc_handle h)
+{
+    if (!h) return MGC_ERR_INVALID;
+    MGC_HIP(h, hipSetDevice(h->device));
+    MgcRange range_("mgc_build");
+    MgcLattice& L = h->L;
+    MgcBuildArgs A{};
+    h->has_prev = false; /* (the snapshot of mgc_edit_markers belongs to the build it was taken in) */
+    h->lut_new_n = 0;    /* (so does a table that waited for an update) */
+    MGC_HIP(h, hipEventRecord(h->ev[0], h->stream));
+    { const int rc = mgc_boundary_args(h, A); if (rc) return rc; }
     A.prob = h->d_prob; A.prob_dtype = h->prob_dtype; A.alpha = h->alpha;
     A.prepush = h->prepush;
-    A.lut = h->lut_n > 0 ? (const double*)h->d_lut : nullptr; A.lut_n = h->lut_n;
     A.fg = h->d_fg; A.bg = h->d_bg; A.tr_in = h->d_tr_in;
     A.tr0 = h->d_tr0; A.fpart = h->d_part; A.tflags = h->d_tflags;
     if ((h->n_edges || h->d_dense) && !L.cap0) { /* explicit edges and dense weight arrays change capacities that the image no longer determines */
@@ -5073,6 +5085,137 @@ int mgc_build(mgc_handle h)
     h->labels_valid = false;
     h->op_spans.clear(); /* (launch-by-launch timing: the pairs of the solve before) */
     h->labels_on_host = false;
+    return MGC_OK;
+}
+
+/* ---- warm update of the boundary term ("The boundary term"): kernels in mgc_nlink_ops.inl ---- */
+static bool mgc_term_by_table(int term)
+{
+    return term == MGC_TERM_DIFFERENCE_EXPONENTIAL || term == MGC_TERM_MAXIMUM_EXPONENTIAL || term == MGC_TERM_DIFFERENCE_POWER || term == MGC_TERM_MAXIMUM_POWER;
+}
+
+int mgc_update_boundary_lut(mgc_handle h, const double* table, int64_t n)
+{
+    if (!h) return MGC_ERR_INVALID;
+    if (n < 0 || n > 65536 || (n > 0 && !table)) return mgc_fail(h, MGC_ERR_INVALID, "mgc_update_boundary_lut: 0 <= n <= 65536 entries");
+    { const int rc = mgc_update_check(h, "mgc_update_boundary_lut"); if (rc) return rc; }
+    MGC_HIP(h, hipSetDevice(h->device));
+    h->lut_new_n = 0;
+    if (n == 0) return MGC_OK;
+    const int rc = mgc_upload(h, &h->d_lut_new, table, (size_t)n * sizeof(double)); /* (a block of its own: the resident table stays readable) */
+    if (rc != MGC_OK) return rc;
+    h->lut_new_n = (int)n;
+    return MGC_OK;
+}
+
+int mgc_update_boundary(mgc_handle h, int term, const void* image, int dtype, double sigma, const double* spacing)
+{
+    if (!h) return MGC_ERR_INVALID;
+    /* every check before the first write: a refused call leaves the handle as it was (a table handed over for the call is dropped) */
+    const int lut_new_n = h->lut_new_n;
+    h->lut_new_n = 0;
+    if (term < MGC_TERM_NONE || term > MGC_TERM_MAXIMUM_POWER) return mgc_fail(h, MGC_ERR_INVALID, "unknown boundary term %d", term);
+    { const int rc = mgc_update_check(h, "mgc_update_boundary"); if (rc) return rc; }
+    MgcLattice& L = h->L;
+    if (L.cap0) return mgc_fail(h, MGC_ERR_UNSUPPORTED, "mgc_update_boundary: the handle holds capacities the image does not determine (explicit edges, dense weight arrays): rebuild (mgc_build)");
+    if (h->build_args.term == MGC_TERM_NONE || !h->d_image) return mgc_fail(h, MGC_ERR_UNSUPPORTED, "mgc_update_boundary: the graph was built without a built-in boundary term: rebuild (mgc_build)");
+    if (term == MGC_TERM_NONE) return mgc_fail(h, MGC_ERR_UNSUPPORTED, "mgc_update_boundary: no term to update to (MGC_TERM_NONE): rebuild (mgc_build)");
+    const size_t es = image ? mgc_dtype_size(dtype) : mgc_dtype_size(h->img_dtype);
+    if (!es) return mgc_fail(h, MGC_ERR_INVALID, "mgc_update_boundary: bad dtype %d", dtype);
+    if (lut_new_n > 0 && !mgc_term_by_table(term))
+        return mgc_fail(h, MGC_ERR_STATE, "mgc_update_boundary: only the exponential and power terms are evaluated by table (the others are IEEE-basic arithmetic)");
+    MGC_HIP(h, hipSetDevice(h->device));
+    MgcRange range_("mgc_update_boundary");
+    /* what can fail for want of memory comes first */
+    if (h->solved && !h->d_labels_prev) { const int rc = mgc_alloc(h, &h->d_labels_prev, h->nvox); if (rc) return rc; }
+    const size_t bytes = (size_t)h->nvox * es;
+    void* d_new = nullptr;
+    if (image) { /* next to the old one, which the fold still reads */
+        MGC_HIP(h, mgc_dmalloc(&d_new, bytes));
+        const hipError_t e = mgc_staged_copy(h, d_new, const_cast<void*>(image), bytes, true);
+        if (e != hipSuccess) { (void)mgc_dfree(d_new); MGC_HIP(h, e); }
+    }
+    if (h->solved) { /* the snapshot rule of mgc_edit_markers: the finished solve's labels are put aside by the two buffers changing hands */
+        std::swap(h->d_labels, h->d_labels_prev);
+        h->has_prev = true;
+    }
+    const MgcBuildArgs A0 = h->build_args;
+    void* const d_old = h->d_image;
+    const size_t old_cap = h->buf_cap[(const void*)&h->d_image];
+    h->term = term;
+    h->sigma = sigma;
+    h->has_spacing = spacing ? 1 : 0;
+    for (int k = 0; k < 3; ++k) h->spacing[k] = 1.0;
+    if (spacing)
+        for (int k = 0; k < h->ndim; ++k) h->spacing[3 - h->ndim + k] = spacing[k];
+    if (image) {
+        h->d_image = d_new;
+        h->img_dtype = dtype;
+        h->range_set = false; /* a range handed over for the previous image does not describe this one */
+        h->buf_cap[(const void*)&h->d_image] = bytes;
+        h->device_bytes += (int64_t)bytes;
+    }
+    std::swap(h->d_lut, h->d_lut_new); /* (d_lut_new now holds the table the graph was built with, until the fold has run) */
+    std::swap(h->buf_cap[(const void*)&h->d_lut], h->buf_cap[(const void*)&h->d_lut_new]);
+    h->lut_n = lut_new_n;
+    MgcBuildArgs A1 = A0;
+    int rc = mgc_boundary_args(h, A1); /* (the *_linear terms: the range of the image resident now) */
+    if (rc == MGC_OK) {
+        const int grid = L.ntiles < h->grid_cap * 4 ? L.ntiles : h->grid_cap * 4;
+        MgcFoldCounts* const d_counts = (MgcFoldCounts*)h->d_part; /* (scratch of a call: nothing in it lives from one call to the next) */
+        const bool table = A0.lut || A1.lut;
+        hipError_t e = hipEventRecord(h->ev[0], h->stream);
+        /* the counters start from zero as after mgc_build (the fold counts the sink tiles) */
+        if (e == hipSuccess) e = hipMemsetAsync(L.count, 0, MGC_NCOUNT * (1 + MGC_NSHARD) * sizeof(int32_t), h->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(d_counts, 0, sizeof(MgcFoldCounts), h->stream);
+        h->zero_mask = 0;
+        h->pending_zero = -1;
+        h->filt[0] = h->filt[1] = 0;
+        if (e == hipSuccess) {
+            if (L.ndir == 6) {
+                if (table) hipLaunchKernelGGL((k_update_nlinks<false, true>), dim3(grid), dim3(MGC_TV), 0, h->stream, L, A0, A1, d_counts);
+                else hipLaunchKernelGGL((k_update_nlinks<false, false>), dim3(grid), dim3(MGC_TV), 0, h->stream, L, A0, A1, d_counts);
+            } else {
+                if (table) hipLaunchKernelGGL((k_update_nlinks<true, true>), dim3(grid), dim3(MGC_TV), 0, h->stream, L, A0, A1, d_counts);
+                else hipLaunchKernelGGL((k_update_nlinks<true, false>), dim3(grid), dim3(MGC_TV), 0, h->stream, L, A0, A1, d_counts);
+            }
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(h->ev[1], h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(&h->fold_counts, d_counts, sizeof(MgcFoldCounts), hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(h->h_count, L.count, MGC_NCOUNT * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
+        const hipError_t e2 = hipStreamSynchronize(h->stream);
+        if (e == hipSuccess) e = e2;
+        if (e != hipSuccess) { h->built = false; rc = mgc_fail(h, MGC_ERR_HIP, "mgc_update_boundary: HIP error %s", hipGetErrorString(e)); }
+    } else {
+        h->built = false; /* (the handle's inputs are the new ones, its graph is not: rebuild) */
+    }
+    if (image) { /* the old block goes back to the pool */
+        (void)mgc_dfree(d_old);
+        h->device_bytes -= (int64_t)old_cap;
+    }
+    if (rc) return rc;
+    h->build_args = A1; /* cut value, getters and mgc_validate see the new inputs */
+    if (L.ndir == 6) h->sink_tiles = h->h_count[MGC_CNT_SINK_TILES];
+    h->zero_mask |= 1u << MGC_CNT_SINK_TILES;
+    float ms = 0.f;
+    MGC_HIP(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+    h->stats.update_ms = ms;
+    h->all_residual = false; /* saturated n-links: the first global relabel of the next solve runs as passes from scratch */
+    h->solved = false;
+    h->labels_valid = false;
+    h->labels_on_host = false;
+    h->op_spans.clear();
+    return MGC_OK;
+}
+
+int mgc_get_boundary_update_info(mgc_handle h, int64_t* out4)
+{
+    if (!h || !out4) return MGC_ERR_INVALID;
+    out4[0] = (int64_t)h->fold_counts.arcs_changed;
+    out4[1] = (int64_t)h->fold_counts.arcs_clamped;
+    out4[2] = (int64_t)h->fold_counts.voxels_changed;
+    out4[3] = (int64_t)h->fold_counts.tiles_flagged;
     return MGC_OK;
 }
 

@@ -89,6 +89,60 @@ def boundary_table(term, image, sigma, limit=65536):
     return boundary_table_for_range(term, sigma, facts[1], facts[2], limit)
 
 
+FACTS_UNKNOWN = "unknown"
+"""what a graph remembers of its image where ``image_table_facts`` was never asked (the term it was built with has no table)"""
+
+
+def _device_image(image):
+    """an image as the library takes it: C-contiguous, in one of its dtypes (bool as uint8, float16 as float32, the rest as float64)"""
+    image = numpy.ascontiguousarray(image)
+    if image.dtype == numpy.bool_:
+        image = image.astype(numpy.uint8)
+    if image.dtype == numpy.float16:
+        image = image.astype(numpy.float32)
+    if image.dtype not in _lib.DTYPE_IDS:
+        image = image.astype(numpy.float64)
+    return image
+
+
+def _term_has_table(term, sigma):
+    return sigma is not None and (term.endswith("exponential") or term.endswith("power"))
+
+
+def normalise_boundary_update(shape, held_facts, boundary_term, boundary_term_args):
+    """What ``VoxelGraph.update_boundary_term`` sends (mgc_update_boundary, include/medpy_hip.h), as a dict: ``term``, ``image``
+    (None: the image the graph holds, else the array as the library takes it), ``sigma``, ``spacing``, ``table`` (the term by
+    table for whole-number images, or None) and ``facts`` (``image_table_facts`` of the image the graph holds afterwards).
+
+    ``boundary_term`` / ``boundary_term_args`` are what ``graph_from_voxels`` takes; the image in the tuple may be None.
+    ``held_facts``: the table facts of the image the graph holds, ``FACTS_UNKNOWN`` where they were never taken.  Pure host code.
+    NotImplementedError for ``boundary_precomputed``, for an image of another shape than the graph's, and for an exponential /
+    power term on a kept image whose facts are unknown (hand the image over again); ValueError for a callable that records no
+    boundary term."""
+    shape = tuple(int(s) for s in shape)
+    rec = _BoundaryRecorder(shape)
+    boundary_term(rec, boundary_term_args)
+    if rec.recorded is None:
+        raise ValueError("update_boundary_term: %r recorded no built-in boundary term" % (boundary_term,))
+    term, image, sigma, spacing = rec.recorded
+    facts = held_facts
+    if image is not None:
+        image = numpy.asarray(image)
+        if image.shape != shape:
+            raise NotImplementedError("medpy_amd: update_boundary_term with an image of shape %s on a graph of shape %s: build it "
+                                      "again with graph_from_voxels" % (image.shape, shape))
+        image = _device_image(image)
+        facts = image_table_facts(term, image) if _term_has_table(term, sigma) else FACTS_UNKNOWN
+    table = None
+    if _term_has_table(term, sigma):
+        if isinstance(facts, str):
+            raise NotImplementedError("medpy_amd: update_boundary_term to an exponential / power term on a graph built with another "
+                                      "kind of term: whether its image holds whole numbers was never looked at, pass the image again")
+        if facts is not None and facts[0]:
+            table = boundary_table_for_range(term, sigma, facts[1], facts[2])
+    return {"term": term, "image": image, "sigma": sigma, "spacing": tuple(spacing) if spacing else None, "table": table, "facts": facts}
+
+
 def _edit_ids(shape, ids, what):
     """one argument of VoxelGraph.edit_markers as a sorted int64 array of distinct flat ids"""
     if ids is None:
@@ -232,6 +286,7 @@ class VoxelGraph(object):
             raise _lib.MedpyHipError(rc, msg)
         self._nodes = int(numpy.prod(self._shape))
         self._labels = None
+        self._table_facts = FACTS_UNKNOWN
         _lib.apply_env_params(self._h)
 
     # -- life cycle
@@ -251,19 +306,17 @@ class VoxelGraph(object):
 
     # -- inputs (called by GCGraph)
     def _set_boundary(self, term, image, sigma, spacing):
-        image = numpy.ascontiguousarray(image)
-        if image.dtype == numpy.bool_:
-            image = image.astype(numpy.uint8)
-        if image.dtype == numpy.float16:
-            image = image.astype(numpy.float32)
-        if image.dtype not in _lib.DTYPE_IDS:
-            image = image.astype(numpy.float64)
+        image = _device_image(image)
         sp = None
         if spacing:
             sp = (C.c_double * len(self._shape))(*[float(s) for s in spacing])
         self._call("mgc_set_boundary", _lib.TERM_IDS[term], _lib.ptr(image), _lib.DTYPE_IDS[image.dtype],
                    float(sigma) if sigma is not None else 0.0, sp)
-        table = boundary_table(term, image, sigma)
+        # (what update_boundary_term needs to know of an image it is told to keep: taken where the table asks for it anyway)
+        self._table_facts = image_table_facts(term, image) if _term_has_table(term, sigma) else FACTS_UNKNOWN
+        table = None
+        if not isinstance(self._table_facts, str) and self._table_facts is not None and self._table_facts[0]:
+            table = boundary_table_for_range(term, sigma, self._table_facts[1], self._table_facts[2])
         if table is not None:
             self._call("mgc_set_boundary_lut", _lib.ptr(table), table.size)
 
@@ -312,6 +365,31 @@ class VoxelGraph(object):
         prob = self._prob_array(probability_map)
         self._labels = None
         self._call("mgc_update_regional_probability", _lib.ptr(prob), _lib.DTYPE_IDS[prob.dtype], float(alpha))
+
+    def update_boundary_term(self, boundary_term, boundary_term_args):
+        """Replace the boundary term: the same ``energy_voxel`` function and argument tuple as ``graph_from_voxels`` takes --
+        another sigma, another term, the spacing, another image of the same shape; an image of None in the tuple means the image
+        the graph holds (nothing is uploaded).  The residual graph is kept and the change of every n-link folded into it
+        ("The boundary term"): the next ``maxflow()`` is a warm solve with the labels and the flow of
+        ``graph_from_voxels`` of the new arguments.  If the graph holds a finished cut its labels are kept on the device, so
+        ``changed_labels()`` and ``labels(out=previous)`` work afterwards.  NotImplementedError for ``boundary_precomputed`` and
+        for an image of another shape; MedpyHipError (ERR_UNSUPPORTED) on graphs with explicit edges or dense weight arrays."""
+        u = normalise_boundary_update(self._shape, self._table_facts, boundary_term, boundary_term_args)
+        sp = (C.c_double * len(self._shape))(*[float(v) for v in u["spacing"]]) if u["spacing"] else None
+        image = u["image"]
+        if u["table"] is not None:
+            self._call("mgc_update_boundary_lut", _lib.ptr(u["table"]), u["table"].size)
+        self._labels = None
+        self._call("mgc_update_boundary", _lib.TERM_IDS[u["term"]], None if image is None else _lib.ptr(image),
+                   _lib.DTYPE_IDS[image.dtype] if image is not None else 0, float(u["sigma"]) if u["sigma"] is not None else 0.0, sp)
+        self._table_facts = u["facts"]
+
+    def boundary_update_info(self):
+        """of the last ``update_boundary_term``: arcs whose capacity changed, arcs whose flow no longer fitted, voxels whose excess
+        or residual sink link changed, tiles that gained a t-link flag (mgc_get_boundary_update_info)"""
+        out = numpy.zeros(4, dtype=numpy.int64)
+        self._call("mgc_get_boundary_update_info", _lib.ptr(out))
+        return dict(zip(("arcs_changed", "arcs_clamped", "voxels_changed", "tiles_flagged"), out.tolist()))
 
     # -- edits by list (DESIGN 10)
     def edit_markers(self, fg=None, bg=None, erase=None):
@@ -569,6 +647,11 @@ class SparseGraph(object):
     def update_regional_term(self, probability_map, alpha):
         """Warm updates exist for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
         raise NotImplementedError("medpy_amd: update_regional_term is implemented for the voxel lattice solver (1-D..3-D volumes, "
+                                  "VoxelGraph) only; this graph went to the sparse-graph solver: build it again from the new inputs")
+
+    def update_boundary_term(self, boundary_term, boundary_term_args):
+        """Warm updates exist for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
+        raise NotImplementedError("medpy_amd: update_boundary_term is implemented for the voxel lattice solver (1-D..3-D volumes, "
                                   "VoxelGraph) only; this graph went to the sparse-graph solver: build it again from the new inputs")
 
     def edit_markers(self, fg=None, bg=None, erase=None):
@@ -1132,6 +1215,10 @@ class EmbeddedLatticeGraph(object):
         raise NotImplementedError("medpy_amd: update_regional_term is not implemented for a graph whose boundary image has another "
                                   "shape than its markers (EmbeddedLatticeGraph): build it again with graph_from_voxels")
 
+    def update_boundary_term(self, boundary_term, boundary_term_args):
+        raise NotImplementedError("medpy_amd: update_boundary_term is not implemented for a graph whose boundary image has another "
+                                  "shape than its markers (EmbeddedLatticeGraph): build it again with graph_from_voxels")
+
     def edit_markers(self, fg=None, bg=None, erase=None):
         raise NotImplementedError("medpy_amd: edit_markers is not implemented for a graph whose boundary image has another shape "
                                   "than its markers (EmbeddedLatticeGraph): build it again with graph_from_voxels")
@@ -1516,3 +1603,26 @@ class GCGraph(object):
 
     def get_edge_count(self):
         return self.__edges
+
+
+class _BoundaryRecorder(GCGraph):
+    """What ``VoxelGraph.update_boundary_term`` hands to an ``energy_voxel`` boundary function in place of the facade: it notes the
+    one built-in term the function records (``recorded`` = (term, image, sigma, spacing), the image as given, None allowed) and
+    refuses everything else a boundary function could do to a graph."""
+
+    def __init__(self, shape):
+        shape = tuple(int(s) for s in shape)
+        GCGraph.__init__(self, int(numpy.prod(shape)), 0, shape=shape)
+        self.recorded = None
+
+    def record_boundary(self, term, image, sigma, spacing):
+        if self.recorded is not None:
+            raise NotImplementedError("medpy_amd: only one built-in boundary term per graph")
+        self.recorded = (term, image, sigma, spacing)
+
+    def set_nweights_dense(self, offset_or_axis, weight_there, weight_back=None):
+        raise NotImplementedError("medpy_amd: update_boundary_term takes the built-in boundary terms; weights the caller evaluated "
+                                  "(boundary_precomputed, set_nweights_dense) are part of a cold build: graph_from_voxels")
+
+    def set_nweight(self, node_from, node_to, weight_there, weight_back):
+        raise NotImplementedError("medpy_amd: update_boundary_term takes the built-in boundary terms, not edges set one by one")
