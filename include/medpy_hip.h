@@ -210,7 +210,9 @@ int mgc_labels_delta(mgc_handle h, int64_t cap, int64_t* ids, int64_t* n);
  * run.  Without it the new term is evaluated without a table.  MGC_ERR_STATE from mgc_update_boundary if the new term has none.
  *   States as for mgc_update_markers (MGC_ERR_STATE before mgc_build, after a solve that did not converge, on a slab handle);
  * MGC_ERR_UNSUPPORTED on a handle whose capacities the image does not determine (explicit edges, dense weight arrays), on a
- * handle built without a boundary term, and for term == MGC_TERM_NONE.  A refused call leaves the handle as it was.  If the
+ * handle built without a boundary term, and for term == MGC_TERM_NONE.  A handle whose n-links were edited by arc list
+ * (mgc_edit_nweights) holds its capacities as built from the first such edit on and is refused for the same reason, until
+ * the end of its life.  A refused call leaves the handle as it was.  If the
  * handle holds a finished solve its labels are put aside as by mgc_edit_markers: mgc_labels_delta after the next mgc_maxflow
  * reports what the new arguments flipped.
  *   mgc_get_boundary_update_info: of the last update, out4 = {arcs whose capacity changed, arcs whose flow no longer fitted,
@@ -218,6 +220,35 @@ int mgc_labels_delta(mgc_handle h, int64_t cap, int64_t* ids, int64_t* n);
 int mgc_update_boundary(mgc_handle h, int term, const void* image, int dtype, double sigma, const double* spacing);
 int mgc_update_boundary_lut(mgc_handle h, const double* table, int64_t n);
 int mgc_get_boundary_update_info(mgc_handle h, int64_t* out4);
+
+/* EDITS OF N-LINKS BY ARC LIST: the local n-link correction of the interactive loop -- a barrier drawn where the cut leaked
+ * through a gap in the edge map, glue across a spurious edge ("Edits of n-links by list").  Arguments as for
+ * mgc_add_edges, but with REPLACE semantics: after the call the capacity as built of the arc i[k] -> j[k] is cap[k] and that of
+ * j[k] -> i[k] is rev[k] (rev == NULL: rev = cap).  0 makes a one-way arc or, both ways, a barrier.  Only the listed arcs are
+ * touched: the flow the residual graph holds on them is clamped to the new capacities, what no longer fits goes back to the
+ * arcs' ends as signed excess (Kohli & Torr's dynamic graph cuts, directed form), and the next mgc_maxflow is a warm solve with
+ * the labels, flow and mgc_validate of a cold build of the edited capacities.  Valid on a built handle before or after
+ * mgc_maxflow, both neighbourhoods, whatever the capacities came from (built-in term, dense arrays, explicit edges).
+ *   States as for mgc_update_markers: MGC_ERR_STATE before mgc_build, on a slab handle, after a solve that did not converge.
+ * n == 0 is MGC_OK and changes nothing, a finished solve included.  The list is checked on the host before anything is
+ * written, and a refused call leaves the handle exactly as it was: MGC_ERR_INVALID for an id outside [0, nvox), a capacity
+ * that is not finite and >= 0, and an unordered pair that is in the list twice (in either orientation); MGC_ERR_UNSUPPORTED
+ * for (i, j) that are not neighbours of the handle's lattice; mgc_last_error names the first offending entry.
+ *   A handle whose capacities the image determines gets them written out on the first edit (8 * ndir bytes per voxel, as for
+ * explicit edges; MGC_ERR_OOM before anything changed if that cannot be had), and stays such a handle: mgc_update_boundary
+ * refuses it from then on.
+ *   The edits stay with the handle as a list on the host, keyed by the pair; a later edit of a pair replaces the earlier one.
+ * mgc_build applies the list last -- boundary term, dense store, batch of mgc_add_edges, then these (replace) -- so a cold rebuild
+ * after new markers or another sigma keeps the barriers.  mgc_clear_nweight_edits forgets the list and makes the handle unbuilt,
+ * as mgc_clear_nweights does.
+ *   If the handle holds a finished solve its labels are put aside as by mgc_edit_markers: mgc_labels_delta after the next
+ * mgc_maxflow reports what the edit flipped; further edits before that solve keep the copy.  After a call that went through,
+ * mgc_last_error holds a note of where its device time went (cap0_fill_ms, fold_ms, refresh_ms).
+ *   mgc_get_nweight_edit_info: out4 = {pairs in the list, and of the last mgc_edit_nweights: pairs whose capacity changed
+ * bitwise, arcs whose flow no longer fitted, voxels whose excess or residual sink link changed}. */
+int mgc_edit_nweights(mgc_handle h, int64_t n, const int64_t* i, const int64_t* j, const double* cap, const double* rev);
+int mgc_clear_nweight_edits(mgc_handle h);
+int mgc_get_nweight_edit_info(mgc_handle h, int64_t* out4);
 
 /* After mgc_maxflow (or the slab driver's last step): see mgc_validation.  Also works on a graph whose solve was cut
  * short (MGC_ERR_NOT_CONVERGED): it then reports the excess that is still active.  MGC_ERR_STATE before the first solve

@@ -138,6 +138,9 @@ SIGNATURES = {
     "mgc_update_boundary": (_INT, [_VP, _INT, _VP, _INT, _DBL, C.POINTER(_DBL)]),
     "mgc_update_boundary_lut": (_INT, [_VP, _VP, _I64]),
     "mgc_get_boundary_update_info": (_INT, [_VP, _VP]),
+    "mgc_edit_nweights": (_INT, [_VP, _I64, _VP, _VP, _VP, _VP]),
+    "mgc_clear_nweight_edits": (_INT, [_VP]),
+    "mgc_get_nweight_edit_info": (_INT, [_VP, _VP]),
     "mgc_add_edges": (_INT, [_VP, _I64, _VP, _VP, _VP, _VP]),
     "mgc_set_tweights_merged": (_INT, [_VP, _VP, _DBL]),
     "mgc_add_nweights": (_INT, [_VP, C.POINTER(_INT), _VP, _VP, _INT]),

@@ -257,6 +257,22 @@ MGC_HD void mgc_node_to_tile(const MgcLattice& L, int64_t id, int& tile, int& lo
     loc = mgc_local((int)(z & 7), (int)(y & 7), (int)(x & 7));
 }
 
+/* direction index of the arc i -> j (node ids) in a lattice with L.ndir neighbours, or -1 when they are not
+ * neighbours there (6: 0 = -x .. 5 = +z; 26: (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1) without the centre, the encoding of mgc26_offset) */
+MGC_HD int mgc_arc_direction(const MgcLattice& L, int64_t i, int64_t j)
+{
+    const int64_t xi = i % L.dx, yi = (i / L.dx) % L.dy, zi = i / (L.dx * L.dy);
+    const int64_t xj = j % L.dx, yj = (j / L.dx) % L.dy, zj = j / (L.dx * L.dy);
+    const int64_t dz = zj - zi, dy = yj - yi, dx = xj - xi;
+    if (dz < -1 || dz > 1 || dy < -1 || dy > 1 || dx < -1 || dx > 1 || (!dz && !dy && !dx)) return -1;
+    if (L.ndir == 6) {
+        if ((dz != 0) + (dy != 0) + (dx != 0) != 1) return -1;
+        return dx ? (dx > 0 ? 1 : 0) : (dy ? (dy > 0 ? 3 : 2) : (dz > 0 ? 5 : 4));
+    }
+    const int c = (int)((dz + 1) * 9 + (dy + 1) * 3 + (dx + 1));
+    return c < 13 ? c : c - 1;
+}
+
 /* Z-slab split of a volume with D0 planes over `nranks` slabs at tile-layer granularity (shared by the
  * HIP library and the host simulator so both cut the volume identically). */
 struct MgcSlabSpec {

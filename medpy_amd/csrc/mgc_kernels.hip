@@ -48,6 +48,7 @@
 #include "mgc_driver.inl"
 #include "mgc_edit_ops.inl"
 #include "mgc_dense_ops.inl"
+#include "mgc_nlink_edit.h"
 
 #define MGC_MARKER_MAX 65535.0              /* GCGraph.MAX, graph.py:288-291 */
 
@@ -1929,21 +1930,6 @@ static void mgc_launch_build(int term, int grid, hipStream_t stream, const MgcLa
 }
 
 
-/* direction index of the arc i -> j (node ids) in a lattice with `ndir` neighbours, or -1 */
-MGC_HD int mgc_arc_direction(const MgcLattice& L, int64_t i, int64_t j)
-{
-    const int64_t xi = i % L.dx, yi = (i / L.dx) % L.dy, zi = i / (L.dx * L.dy);
-    const int64_t xj = j % L.dx, yj = (j / L.dx) % L.dy, zj = j / (L.dx * L.dy);
-    const int64_t dz = zj - zi, dy = yj - yi, dx = xj - xi;
-    if (dz < -1 || dz > 1 || dy < -1 || dy > 1 || dx < -1 || dx > 1 || (!dz && !dy && !dx)) return -1;
-    if (L.ndir == 6) {
-        if ((dz != 0) + (dy != 0) + (dx != 0) != 1) return -1;
-        return dx ? (dx > 0 ? 1 : 0) : (dy ? (dy > 0 ? 3 : 2) : (dz > 0 ? 5 : 4));
-    }
-    const int c = (int)((dz + 1) * 9 + (dy + 1) * 3 + (dx + 1));
-    return c < 13 ? c : c - 1;
-}
-
 /* plug-in path: explicit lattice edges accumulate like Graph::sum_edge (graph.h:457-480): every arc slot receives its
  * contributions ONE AFTER THE OTHER in call order, on top of the weight k_build left there -- the same floating point
  * additions in the same order as the reference, so repeated edges give bit-identical capacities (an atomicAdd per
@@ -2098,6 +2084,8 @@ __device__ __forceinline__ double mgc_built_capacity(const MgcLattice& L, const 
     if (A.has_spacing) w = w / (L.ndir == 6 ? A.inv_axis[d >> 1] : A.div26[d]);
     return w;
 }
+
+#include "mgc_nlink_edit_ops.inl"
 
 /* capacity of the cut (S = label 1, T = label 0) from the capacities as built */
 __global__ __launch_bounds__(MGC_TV) void k_cut_value(MgcLattice L, MgcBuildArgs A, const double* tr0, const uint8_t* labels, double* part)
@@ -2769,6 +2757,11 @@ struct mgc_graph {
     std::vector<double*> dense_extra[26];
     int dense_given[26] = {};
     const double** d_dense_planes = nullptr;
+    /* mgc_edit_nweights: the capacities the caller set by arc list, kept on the host (strokes are small) and applied last by every
+       build: (lower id, higher id) -> (capacity lower -> higher, capacity higher -> lower); a later edit of a pair replaces the
+       earlier one.  edit_info: what mgc_get_nweight_edit_info reports of the last call ([0] is the size of the list) */
+    std::map<std::pair<int64_t, int64_t>, std::pair<double, double>> nw_over;
+    int64_t edit_info[4] = {0, 0, 0, 0};
     std::map<const void*, size_t> buf_cap; /* capacity of the buffers mgc_upload manages, keyed by the owning field */
     /* outputs / scratch */
     uint8_t* d_tsum = nullptr;   /* per tile: on which side of the cut its voxels lie (k_labels8) */
@@ -4479,6 +4472,8 @@ static int mgc_update_check(mgc_handle h, const char* what)
     return MGC_OK;
 }
 
+static int mgc_edit_overrides(mgc_handle h);
+
 static int mgc_update_tlinks(mgc_handle h)
 {
     MgcRange range_("mgc_update_tlinks");
@@ -4956,6 +4951,153 @@ int mgc_clear_nweights(mgc_handle h)
     return MGC_OK;
 }
 
+/* ---- edits of n-links by arc list ("Edits of n-links by list"): host preparation in mgc_nlink_edit.h, kernels in mgc_nlink_edit_ops.inl ---- */
+
+/* The fold of a checked list into the state the handle holds (L.cap0 exists): plan, upload, k_edit_gather, k_edit_nlinks.  Waits for
+ * the stream.  info3 (or NULL): pairs whose capacity changed bitwise, arcs clamped, voxels changed; *fold_ms: device time. */
+static int mgc_edit_fold(mgc_handle h, int64_t n, const int64_t* i, const int64_t* j, const double* cap, const double* rev, int64_t* info3, float* fold_ms)
+{
+    MgcLattice& L = h->L;
+    MgcEditPlan P;
+    mgc_edit_plan(L, n, i, j, cap, rev, &P);
+    const size_t m = P.slot.size(), nt = P.tile.size();
+    const int grid = (int)std::min<size_t>(nt, MGC_EDIT_MAX_WAVES);
+    /* one block: [slot | c_out1 | c_in1 | old (device only) | counts (device only) | partner | tile | begin] */
+    const size_t at_out = m * 8, at_in = 2 * m * 8, at_old = 3 * m * 8, at_cnt = 4 * m * 8, at_partner = at_cnt + (size_t)grid * sizeof(MgcEditCounts);
+    const size_t at_tile = at_partner + m * 4, at_begin = at_tile + nt * 4, bytes = at_begin + (nt + 1) * 4;
+    std::vector<char> host(bytes, 0);
+    memcpy(host.data(), P.slot.data(), m * 8);
+    memcpy(host.data() + at_out, P.c_out1.data(), m * 8);
+    memcpy(host.data() + at_in, P.c_in1.data(), m * 8);
+    memcpy(host.data() + at_partner, P.partner.data(), m * 4);
+    memcpy(host.data() + at_tile, P.tile.data(), nt * 4);
+    memcpy(host.data() + at_begin, P.begin.data(), (nt + 1) * 4);
+    void* p = nullptr; void* own = nullptr;
+    { const int rc = mgc_call_scratch(h, 0, bytes, &p, &own); if (rc) return rc; }
+    char* const d = (char*)p;
+    std::vector<MgcEditCounts> counts((size_t)grid);
+    hipError_t e = hipMemcpyAsync(d, host.data(), bytes, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipEventRecord(h->ev[2], h->stream);
+    if (e == hipSuccess) {
+        const int64_t wgs = ((int64_t)m + 255) / 256;
+        hipLaunchKernelGGL(k_edit_gather, dim3((unsigned)(wgs < 1024 ? wgs : 1024)), dim3(256), 0, h->stream, (int64_t)m, (const int64_t*)d, (const double*)L.cap0, (double*)(d + at_old));
+        if (L.ndir == 6)
+            hipLaunchKernelGGL((k_edit_nlinks<false>), dim3(grid), dim3(64), 0, h->stream, L, h->d_tr0, h->d_tflags, (int)nt, (const int32_t*)(d + at_tile), (const int32_t*)(d + at_begin),
+                               (const int64_t*)d, (const int32_t*)(d + at_partner), (const double*)(d + at_out), (const double*)(d + at_in), (const double*)(d + at_old), (MgcEditCounts*)(d + at_cnt));
+        else
+            hipLaunchKernelGGL((k_edit_nlinks<true>), dim3(grid), dim3(64), 0, h->stream, L, h->d_tr0, h->d_tflags, (int)nt, (const int32_t*)(d + at_tile), (const int32_t*)(d + at_begin),
+                               (const int64_t*)d, (const int32_t*)(d + at_partner), (const double*)(d + at_out), (const double*)(d + at_in), (const double*)(d + at_old), (MgcEditCounts*)(d + at_cnt));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(h->ev[3], h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(counts.data(), d + at_cnt, (size_t)grid * sizeof(MgcEditCounts), hipMemcpyDeviceToHost, h->stream);
+    const hipError_t e2 = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess) e = e2;
+    (void)mgc_dfree(own);
+    MGC_HIP(h, e);
+    if (info3) {
+        info3[0] = info3[1] = info3[2] = 0;
+        for (const MgcEditCounts& c : counts) { info3[0] += c.pairs_changed; info3[1] += c.arcs_clamped; info3[2] += c.voxels_changed; }
+    }
+    if (fold_ms) MGC_HIP(h, hipEventElapsedTime(fold_ms, h->ev[2], h->ev[3]));
+    return MGC_OK;
+}
+
+/* mgc_build: the whole list on the freshly built state, through the path of an edit -- fold, then the refresh of mgc_update_tlinks */
+static int mgc_edit_overrides(mgc_handle h)
+{
+    std::vector<int64_t> i, j;
+    std::vector<double> cap, rev;
+    for (const auto& kv : h->nw_over) {
+        i.push_back(kv.first.first); j.push_back(kv.first.second);
+        cap.push_back(kv.second.first); rev.push_back(kv.second.second);
+    }
+    float ms = 0.f;
+    int rc = mgc_edit_fold(h, (int64_t)i.size(), i.data(), j.data(), cap.data(), rev.data(), nullptr, &ms);
+    if (rc == MGC_OK) rc = mgc_update_tlinks(h);
+    if (rc == MGC_OK) h->stats.update_ms += ms;
+    return rc;
+}
+
+int mgc_edit_nweights(mgc_handle h, int64_t n, const int64_t* i, const int64_t* j, const double* cap, const double* rev)
+{
+    if (!h) return MGC_ERR_INVALID;
+    { const int rc = mgc_update_check(h, "mgc_edit_nweights"); if (rc) return rc; }
+    if (n < 0 || n > ((int64_t)1 << 28) || (n > 0 && (!i || !j || !cap))) return mgc_fail(h, MGC_ERR_INVALID, "mgc_edit_nweights: n = %lld, i / j / cap NULL", (long long)n);
+    if (n == 0) return MGC_OK;
+    MgcLattice& L = h->L;
+    /* every check before the first write: a refused call leaves the handle as it was */
+    {
+        char msg[256];
+        int64_t bad = -1;
+        const int code = mgc_edit_check(L, n, i, j, cap, rev, &bad, msg, sizeof(msg));
+        if (code != MGC_EDIT_OK) return mgc_fail(h, code == MGC_EDIT_NOT_NEIGHBOURS ? MGC_ERR_UNSUPPORTED : MGC_ERR_INVALID, "mgc_edit_nweights: %s", msg);
+    }
+    MGC_HIP(h, hipSetDevice(h->device));
+    MgcRange range_("mgc_edit_nweights");
+    /* what can fail for want of memory comes first */
+    if (h->solved && !h->d_labels_prev) { const int rc = mgc_alloc(h, &h->d_labels_prev, h->nvox); if (rc) return rc; }
+    float fill_ms = 0.f, fold_ms = 0.f;
+    if (!L.cap0) {
+        /* an image-determined graph: its capacities as built are written out once.  The fill evaluates them through
+         * mgc_built_capacity, which goes by L.cap0 -- so the pointer is set only behind the launch */
+        const int64_t count = (int64_t)L.ntiles * MGC_TV * L.ndir;
+        double* fresh = nullptr;
+        MGC_HIP(h, mgc_dmalloc((void**)&fresh, (size_t)count * sizeof(double)));
+        const int grid = L.ntiles < h->grid_cap * 4 ? L.ntiles : h->grid_cap * 4;
+        hipError_t e = hipEventRecord(h->ev[0], h->stream);
+        if (e == hipSuccess) {
+            if (L.ndir == 6) hipLaunchKernelGGL((k_materialise_cap0<false>), dim3(grid), dim3(MGC_TV), 0, h->stream, L, h->build_args, fresh);
+            else hipLaunchKernelGGL((k_materialise_cap0<true>), dim3(grid), dim3(MGC_TV), 0, h->stream, L, h->build_args, fresh);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(h->ev[1], h->stream);
+        const hipError_t e2 = hipStreamSynchronize(h->stream);
+        if (e == hipSuccess) e = e2;
+        if (e != hipSuccess) { (void)mgc_dfree(fresh); MGC_HIP(h, e); }
+        MGC_HIP(h, hipEventElapsedTime(&fill_ms, h->ev[0], h->ev[1]));
+        L.cap0 = fresh;
+        h->device_bytes += count * (int64_t)sizeof(double);
+    }
+    if (h->solved) { /* the snapshot rule of mgc_edit_markers: the finished solve's labels are put aside by the two buffers changing hands */
+        std::swap(h->d_labels, h->d_labels_prev);
+        h->has_prev = true;
+    }
+    for (int64_t k = 0; k < n; ++k) {
+        const double a = cap[k], b = rev ? rev[k] : cap[k];
+        if (i[k] < j[k]) h->nw_over[{i[k], j[k]}] = {a, b};
+        else h->nw_over[{j[k], i[k]}] = {b, a};
+    }
+    h->edit_info[0] = (int64_t)h->nw_over.size();
+    h->edit_info[1] = h->edit_info[2] = h->edit_info[3] = 0;
+    int rc = mgc_edit_fold(h, n, i, j, cap, rev, h->edit_info + 1, &fold_ms);
+    /* an arc that gained capacity can make voxels of untouched tiles reachable again, whose MGC_ST_EXCESS is only "at its last visit":
+     * every status word, the stamps and the count of sink tiles are rewritten from the planes (no voxel changes: the inputs are the same) */
+    if (rc == MGC_OK) rc = mgc_update_tlinks(h);
+    if (rc) { h->built = false; return rc; } /* (a HIP error in the middle of the fold: rebuild) */
+    const double refresh_ms = h->stats.update_ms;
+    h->stats.update_ms += (double)fold_ms;
+    /* no error: the note says where the device time of this call went (tools/gpu_nweight_edit.py records it) */
+    (void)mgc_fail(h, MGC_OK, "mgc_edit_nweights: cap0_fill_ms=%.3f fold_ms=%.3f refresh_ms=%.3f", (double)fill_ms, (double)fold_ms, refresh_ms);
+    return MGC_OK;
+}
+
+int mgc_clear_nweight_edits(mgc_handle h)
+{
+    if (!h) return MGC_ERR_INVALID;
+    h->nw_over.clear();
+    h->edit_info[0] = 0;
+    h->built = h->solved = false;
+    return MGC_OK;
+}
+
+int mgc_get_nweight_edit_info(mgc_handle h, int64_t* out4)
+{
+    if (!h || !out4) return MGC_ERR_INVALID;
+    for (int k = 0; k < 4; ++k) out4[k] = h->edit_info[k];
+    return MGC_OK;
+}
+
 /* the boundary term's part of MgcBuildArgs from what the handle holds now: image, term, sigma, spacing, table (mgc_build, mgc_update_boundary) */
 static int mgc_boundary_args(mgc_handle h, MgcBuildArgs& A)
 {
@@ -5007,7 +5149,7 @@ int mgc_build(mgc_handle h)
     A.prepush = h->prepush;
     A.fg = h->d_fg; A.bg = h->d_bg; A.tr_in = h->d_tr_in;
     A.tr0 = h->d_tr0; A.fpart = h->d_part; A.tflags = h->d_tflags;
-    if ((h->n_edges || h->d_dense) && !L.cap0) { /* explicit edges and dense weight arrays change capacities that the image no longer determines */
+    if ((h->n_edges || h->d_dense || !h->nw_over.empty()) && !L.cap0) { /* explicit edges, dense weight arrays and edits by arc list change capacities that the image no longer determines */
         const int rc = mgc_alloc(h, &L.cap0, (int64_t)L.ntiles * MGC_TV * L.ndir);
         if (rc) return rc;
     }
@@ -5023,7 +5165,8 @@ int mgc_build(mgc_handle h)
     MGC_HIP(h, hipGetLastError());
     mgc_sum_partials(h, (int64_t)L.ntiles, h->d_scalar);
     MGC_HIP(h, hipGetLastError());
-    /* the order is fixed: the boundary term's weight (k_build), then the dense store, then the batch of mgc_add_edges */
+    /* the order is fixed: the boundary term's weight (k_build), then the dense store, then the batch of mgc_add_edges, then --
+     * behind everything else of the build, below -- the capacities set by mgc_edit_nweights */
     if (h->d_dense) {
         MgcDenseLayers X{nullptr, 0};
         for (int d = 0; d < L.ndir; ++d) X.n = std::max(X.n, (int)h->dense_extra[d].size());
@@ -5085,6 +5228,13 @@ int mgc_build(mgc_handle h)
     h->labels_valid = false;
     h->op_spans.clear(); /* (launch-by-launch timing: the pairs of the solve before) */
     h->labels_on_host = false;
+    if (!h->nw_over.empty()) { /* the capacities set by arc list come last and REPLACE what the build left on their arcs */
+        const double build_ms = h->stats.build_ms;
+        const int rc = mgc_edit_overrides(h);
+        if (rc) { h->built = false; return rc; }
+        h->stats.build_ms = build_ms + h->stats.update_ms;
+        h->stats.update_ms = 0.0;
+    }
     return MGC_OK;
 }
 
@@ -5117,7 +5267,7 @@ int mgc_update_boundary(mgc_handle h, int term, const void* image, int dtype, do
     if (term < MGC_TERM_NONE || term > MGC_TERM_MAXIMUM_POWER) return mgc_fail(h, MGC_ERR_INVALID, "unknown boundary term %d", term);
     { const int rc = mgc_update_check(h, "mgc_update_boundary"); if (rc) return rc; }
     MgcLattice& L = h->L;
-    if (L.cap0) return mgc_fail(h, MGC_ERR_UNSUPPORTED, "mgc_update_boundary: the handle holds capacities the image does not determine (explicit edges, dense weight arrays): rebuild (mgc_build)");
+    if (L.cap0) return mgc_fail(h, MGC_ERR_UNSUPPORTED, "mgc_update_boundary: the handle holds capacities the image does not determine (explicit edges, dense weight arrays, n-links edited by arc list): rebuild (mgc_build)");
     if (h->build_args.term == MGC_TERM_NONE || !h->d_image) return mgc_fail(h, MGC_ERR_UNSUPPORTED, "mgc_update_boundary: the graph was built without a built-in boundary term: rebuild (mgc_build)");
     if (term == MGC_TERM_NONE) return mgc_fail(h, MGC_ERR_UNSUPPORTED, "mgc_update_boundary: no term to update to (MGC_TERM_NONE): rebuild (mgc_build)");
     const size_t es = image ? mgc_dtype_size(dtype) : mgc_dtype_size(h->img_dtype);

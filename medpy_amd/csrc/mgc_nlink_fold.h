@@ -51,4 +51,35 @@ MGC_FOLD_HD double mgc_nlink_fold(double c, double c1, double* r, bool* clamped)
     return phi - phi1;
 }
 
+/* The DIRECTED form (mgc_edit_nweights, DESIGN 10, "Edits of n-links by list"): the two arcs of a pair get capacities of their own.
+ * One arc, seen from its tail: c_out / c_in = capacity as built of the arc and of its reverse BEFORE the edit, c_out1 / c_in1 = after
+ * it, *r = the arc's residual capacity.
+ *   both capacities unchanged (bitwise): nothing is touched, returns 0.
+ *   otherwise  phi  = c_out - *r                       net flow out along the arc (negative: flow came in along the reverse arc)
+ *              phi1 = min(max(phi, -c_in1), c_out1)    what the new pair can carry of it
+ *              *r   = c_out1 - phi1                    in [0, c_out1 + c_in1]
+ *   and returns phi - phi1 to the tail's signed excess.  The head evaluates the rule for the reverse arc from its own residual (its
+ *   c_out is this c_in and so on) and gets the opposite amount.  *clamped: phi1 != phi.
+ * With c_in == c_out and c_in1 == c_out1 this is mgc_nlink_fold(c_out, c_out1, r, clamped) bit for bit, the capacities that are not
+ * numbers included; a reverse capacity that is not a number lets no flow come in. */
+MGC_FOLD_HD double mgc_nlink_fold_directed(double c_out, double c_in, double c_out1, double c_in1, double* r, bool* clamped)
+{
+    *clamped = false;
+    if (mgc_same_bits(c_out, c_out1) && mgc_same_bits(c_in, c_in1)) return 0.0;
+    double phi = c_out - *r;
+    if (!(phi == phi)) phi = 0.0;
+    if (!(c_out1 == c_out1)) { /* no capacity to speak of: whatever flowed goes back */
+        *r = c_out1;
+        *clamped = phi != 0.0;
+        return phi;
+    }
+    const double lo = c_in1 == c_in1 ? -c_in1 : 0.0;
+    double phi1 = phi;
+    if (phi1 < lo) phi1 = lo;
+    if (phi1 > c_out1) phi1 = c_out1;
+    *r = c_out1 - phi1;
+    *clamped = phi1 != phi;
+    return phi - phi1;
+}
+
 #endif /* MGC_NLINK_FOLD_H */

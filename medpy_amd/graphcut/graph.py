@@ -195,6 +195,33 @@ def merge_marker_edits(shape, fg=None, bg=None, erase=None):
     return ids, ops
 
 
+def normalise_nweight_edit(nodes_from, nodes_to, weight_there, weight_back=None):
+    """What ``VoxelGraph.edit_nweights`` sends (mgc_edit_nweights, include/medpy_hip.h): ``(i, j, cap, rev)`` -- C-contiguous 1-D
+    arrays of one length, ids int64, capacities float64; ``rev`` is None where ``weight_back`` is (both ways ``weight_there``).
+
+    The arguments have the shape of ``GCGraph.set_nweight``: each a scalar or a 1-D array, scalars are broadcast to the length of
+    the arrays (all scalars: one arc pair).  Pure host code; the library checks ids, neighbourhood, capacities and repeated pairs.
+    ValueError for node ids that are not whole numbers, arrays of more than one axis and arrays of different lengths."""
+    given = [nodes_from, nodes_to, weight_there] + ([] if weight_back is None else [weight_back])
+    names = ("nodes_from", "nodes_to", "weight_there", "weight_back")
+    arrays = [numpy.asarray(a) for a in given]
+    for a, name in zip(arrays, names):
+        if a.ndim > 1:
+            raise ValueError("edit_nweights: %s must be a scalar or a 1-D array, not of shape %s" % (name, a.shape))
+    for a, name in zip(arrays[:2], names):
+        if a.dtype.kind not in "iu":
+            raise ValueError("edit_nweights: %s must hold integers, not %s" % (name, a.dtype))
+    for a, name in zip(arrays[2:], names[2:]):
+        if a.dtype.kind not in "iufb":
+            raise ValueError("edit_nweights: %s of dtype %s" % (name, a.dtype))
+    lengths = {a.shape[0] for a in arrays if a.ndim == 1}
+    if len(lengths) > 1:
+        raise ValueError("edit_nweights: arrays of different lengths %s" % sorted(lengths))
+    n = lengths.pop() if lengths else 1
+    out = [numpy.ascontiguousarray(numpy.broadcast_to(a, (n,)), dtype=numpy.int64 if k < 2 else numpy.float64) for k, a in enumerate(arrays)]
+    return out[0], out[1], out[2], (out[3] if weight_back is not None else None)
+
+
 def pad_skeleton_weights(shape, axis, weights):
     """The per-axis weight array of the reference's ``__skeleton_base`` (energy_voxel.py:644-658: extent - 1 along ``axis``, entry p =
     the pair (p, p + e_axis)) as an array of the full ``shape``: the same entries, and one more slice along ``axis`` that holds
@@ -400,6 +427,33 @@ class VoxelGraph(object):
         self._call("mgc_edit_markers", ids.size, _lib.ptr(ids), _lib.ptr(ops))
         if ids.size:
             self._labels = None
+
+    def edit_nweights(self, nodes_from, nodes_to, weight_there, weight_back=None):
+        """Set the capacities of n-links of the built graph by arc list (REPLACE, not add): afterwards the arc
+        ``nodes_from[k] -> nodes_to[k]`` has capacity ``weight_there[k]`` and its reverse ``weight_back[k]`` (None: the same).
+        Arguments in the shape of ``GCGraph.set_nweight``, scalars or 1-D arrays (``normalise_nweight_edit``); the nodes must be
+        neighbours of the graph's lattice.  0 makes a one-way arc or, both ways, a barrier.  Only the listed arcs are folded into
+        the residual graph ("Edits of n-links by list"): the next ``maxflow()`` is a warm solve with the labels and the
+        flow of a graph built from the edited weights.  The edits stay with the graph -- a rebuild applies them again -- until
+        ``clear_nweight_edits()``.  If the graph holds a finished cut its labels are kept on the device, so ``changed_labels()``
+        and ``labels(out=previous)`` work afterwards.  MedpyHipError: ERR_INVALID / ERR_UNSUPPORTED name the first offending
+        entry (bad id, capacity, pair twice / not neighbours); the graph is then as it was."""
+        i, j, cap, rev = normalise_nweight_edit(nodes_from, nodes_to, weight_there, weight_back)
+        self._call("mgc_edit_nweights", i.size, _lib.ptr(i), _lib.ptr(j), _lib.ptr(cap), None if rev is None else _lib.ptr(rev))
+        if i.size:
+            self._labels = None
+
+    def clear_nweight_edits(self):
+        """mgc_clear_nweight_edits: forget the capacities set by ``edit_nweights``; the graph is unbuilt afterwards"""
+        self._labels = None
+        self._call("mgc_clear_nweight_edits")
+
+    def nweight_edit_info(self):
+        """arc pairs the graph keeps from ``edit_nweights`` and, of the last call: pairs whose capacity changed bitwise, arcs whose
+        flow no longer fitted, voxels whose excess or residual sink link changed (mgc_get_nweight_edit_info)"""
+        out = numpy.zeros(4, dtype=numpy.int64)
+        self._call("mgc_get_nweight_edit_info", _lib.ptr(out))
+        return dict(zip(("pairs_kept", "pairs_changed", "arcs_clamped", "voxels_changed"), out.tolist()))
 
     def markers(self):
         """(fg, bg): the markers the graph holds now, bool arrays of the volume's shape"""
@@ -658,6 +712,21 @@ class SparseGraph(object):
         """Edits by list exist for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
         raise NotImplementedError("medpy_amd: edit_markers is implemented for the voxel lattice solver (1-D..3-D volumes, "
                                   "VoxelGraph) only; this graph went to the sparse-graph solver: build it again from the new inputs")
+
+    def edit_nweights(self, nodes_from, nodes_to, weight_there, weight_back=None):
+        """Edits by list exist for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
+        raise NotImplementedError("medpy_amd: edit_nweights is implemented for the voxel lattice solver (1-D..3-D volumes, "
+                                  "VoxelGraph) only; this graph went to the sparse-graph solver: build it again from the new inputs")
+
+    def clear_nweight_edits(self):
+        """Edits by list exist for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
+        raise NotImplementedError("medpy_amd: clear_nweight_edits is implemented for the voxel lattice solver (1-D..3-D volumes, "
+                                  "VoxelGraph) only; this graph went to the sparse-graph solver: build it again from the new inputs")
+
+    def nweight_edit_info(self):
+        """Edits by list exist for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
+        raise NotImplementedError("medpy_amd: nweight_edit_info is implemented for the voxel lattice solver (1-D..3-D volumes, "
+                                  "VoxelGraph) only; this graph went to the sparse-graph solver")
 
     def changed_labels(self):
         """Edits by list exist for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
@@ -1222,6 +1291,18 @@ class EmbeddedLatticeGraph(object):
     def edit_markers(self, fg=None, bg=None, erase=None):
         raise NotImplementedError("medpy_amd: edit_markers is not implemented for a graph whose boundary image has another shape "
                                   "than its markers (EmbeddedLatticeGraph): build it again with graph_from_voxels")
+
+    def edit_nweights(self, nodes_from, nodes_to, weight_there, weight_back=None):
+        raise NotImplementedError("medpy_amd: edit_nweights is not implemented for a graph whose boundary image has another shape "
+                                  "than its markers (EmbeddedLatticeGraph): build it again with graph_from_voxels")
+
+    def clear_nweight_edits(self):
+        raise NotImplementedError("medpy_amd: clear_nweight_edits is not implemented for a graph whose boundary image has another "
+                                  "shape than its markers (EmbeddedLatticeGraph): build it again with graph_from_voxels")
+
+    def nweight_edit_info(self):
+        raise NotImplementedError("medpy_amd: nweight_edit_info is not implemented for a graph whose boundary image has another "
+                                  "shape than its markers (EmbeddedLatticeGraph)")
 
     def changed_labels(self):
         raise NotImplementedError("medpy_amd: changed_labels is not implemented for a graph whose boundary image has another shape "
