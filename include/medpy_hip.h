@@ -296,6 +296,42 @@ int mgc_set_tweights_merged(mgc_handle h, const double* tr, double flow_const);
 int mgc_add_nweights(mgc_handle h, const int* offset, const void* there, const void* back, int dtype);
 int mgc_clear_nweights(mgc_handle h);
 
+/* Dense t-link weight arrays: the bulk form of GCGraph.set_tweight (graph.py:466-498), for regional terms the caller evaluates
+ * itself (negative log-likelihoods of a mixture model or a histogram, the output of a network); DESIGN 12.  `source` and `sink`
+ * are C-contiguous arrays of the handle's shape, dtype MGC_F32 or MGC_F64 (f32 is widened on the device, which is exact).
+ *   Semantics of Graph::add_tweights (graph.h:416-425), one call per voxel on the handle's explicit t-link: calls accumulate in
+ * call order, the part both weights share goes into the flow constant.  Negative weights are allowed, as in the reference; every
+ * entry must be finite.  The arrays are checked on the device before the first write: MGC_ERR_INVALID, with mgc_last_error
+ * naming the array, the flat index and the value of the first offender, and the handle exactly as it was.
+ *   The first call allocates the STORE that stays with the handle: two f64 per voxel in C order -- the merged explicit t-link,
+ * which builds and warm updates read where they read the vector of mgc_set_tweights_merged, and the voxel's share of the flow
+ * constant -- plus one partial sum per 4096 voxels.  The flow constant of the store is the sum of the share plane in a fixed
+ * order.  The merge order of a build stays: explicit t-links, regional probability map, fg markers, bg markers.  The call makes
+ * a built handle unbuilt.  mgc_clear_tweights forgets and frees the explicit t-links (of either origin) and makes the handle
+ * unbuilt.  MGC_ERR_UNSUPPORTED on a slab handle.  After a call that went through, mgc_last_error holds a note of where its
+ * time went (upload_ms, check_ms, accumulate_ms).
+ *   The store and mgc_set_tweights_merged are exclusive on one handle (a merged vector comes with a flow constant whose
+ * per-voxel shares are unknown): whichever comes second returns MGC_ERR_STATE until mgc_clear_tweights.
+ *   mgc_update_tweights: the warm form, on a built handle (states as for mgc_update_markers).  Afterwards the store holds
+ * exactly what mgc_clear_tweights and one mgc_add_tweights of these arrays leave, the change of every voxel's merged t-link is
+ * folded into the residual graph as by mgc_update_markers, and the next mgc_maxflow is a warm solve.  Checked before the first
+ * write.  Drops the label snapshot of mgc_labels_delta.
+ *   mgc_edit_tweights: by voxel list, REPLACE as mgc_edit_nweights: afterwards the explicit t-link of voxel ids[k] is what one
+ * add_tweights of (source[k], sink[k]) leaves on a zero t-link: tr = source - sink, share min(source, sink).  A handle without a
+ * store gets a zeroed one first (MGC_ERR_OOM before anything changed).  The list is checked on the host before the first write:
+ * MGC_ERR_INVALID for an id outside [0, nvox), a weight that is not finite, an id given twice; mgc_last_error names the first
+ * offending entry.  n == 0 is MGC_OK and changes nothing, a finished solve included.  MGC_ERR_STATE before mgc_build, on a slab
+ * handle, after a solve that did not converge, and when the explicit t-links came from mgc_set_tweights_merged.  The labels of
+ * a finished solve are put aside as by mgc_edit_markers, so mgc_labels_delta works after the next solve.  The edits live in the
+ * store: a later mgc_build sees them.
+ *   mgc_get_tweight_edit_info: out4 = {store held (0 / 1), dense calls accumulated since the last clear, entries of the last
+ * list call, voxels whose explicit t-link changed bitwise in the last update or edit}. */
+int mgc_add_tweights(mgc_handle h, const void* source, const void* sink, int dtype);
+int mgc_clear_tweights(mgc_handle h);
+int mgc_update_tweights(mgc_handle h, const void* source, const void* sink, int dtype);
+int mgc_edit_tweights(mgc_handle h, int64_t n, const int64_t* ids, const double* source, const double* sink);
+int mgc_get_tweight_edit_info(mgc_handle h, int64_t* out4);
+
 /* Runs the n-link / t-link kernels: the residual graph is now resident in HBM. */
 int mgc_build(mgc_handle h);
 

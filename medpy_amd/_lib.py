@@ -145,6 +145,11 @@ SIGNATURES = {
     "mgc_set_tweights_merged": (_INT, [_VP, _VP, _DBL]),
     "mgc_add_nweights": (_INT, [_VP, C.POINTER(_INT), _VP, _VP, _INT]),
     "mgc_clear_nweights": (_INT, [_VP]),
+    "mgc_add_tweights": (_INT, [_VP, _VP, _VP, _INT]),
+    "mgc_clear_tweights": (_INT, [_VP]),
+    "mgc_update_tweights": (_INT, [_VP, _VP, _VP, _INT]),
+    "mgc_edit_tweights": (_INT, [_VP, _I64, _VP, _VP, _VP]),
+    "mgc_get_tweight_edit_info": (_INT, [_VP, _VP]),
     "mgc_build": (_INT, [_VP]),
     "mgc_get_nweights": (_INT, [_VP, _INT, _VP]),
     "mgc_get_tweights": (_INT, [_VP, _VP]),

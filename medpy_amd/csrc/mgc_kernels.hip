@@ -2086,6 +2086,7 @@ __device__ __forceinline__ double mgc_built_capacity(const MgcLattice& L, const 
 }
 
 #include "mgc_nlink_edit_ops.inl"
+#include "mgc_tweight_ops.inl"
 
 /* capacity of the cut (S = label 1, T = label 0) from the capacities as built */
 __global__ __launch_bounds__(MGC_TV) void k_cut_value(MgcLattice L, MgcBuildArgs A, const double* tr0, const uint8_t* labels, double* part)
@@ -2743,6 +2744,13 @@ struct mgc_graph {
     MgcFoldCounts fold_counts{}; /* of the last mgc_update_boundary (mgc_get_boundary_update_info) */
     uint8_t* d_fg = nullptr; uint8_t* d_bg = nullptr;
     double* d_tr_in = nullptr; double flow_const_in = 0;
+    /* dense t-link weight arrays (mgc_add_tweights, mgc_tweight_ops.inl): d_tr_in is then the STORE -- the plane of merged explicit
+       t-links, and behind it (from entry nvox rounded up to even on) the plane of the voxels' shares of the flow constant -- and
+       flow_const_in the fixed-order sum of the share plane: d_tw_part holds the segment partials and, behind them, their sum.
+       tw_info: what mgc_get_tweight_edit_info reports after "store held" */
+    bool tw_store = false;
+    double* d_tw_part = nullptr;
+    int64_t tw_info[3] = {0, 0, 0};
     /* pending explicit edges (host copy kept until build) */
     MgcBuildArgs build_args{}; /* of the last mgc_build: the built capacities are re-evaluated from it (mgc_built_capacity) */
     /* explicit lattice edges (plug-in path), kept until the next build: 2n arc contributions sorted by arc slot, call order
@@ -4252,7 +4260,7 @@ int mgc_destroy(mgc_handle h)
     void* ptrs[] = {L.rcap, L.cap0, L.excess, L.sink, L.height, L.rmask, L.rmask32, L.obox, L.oflags, L.list[0], L.list[1], L.list[2],
                     L.list[3], L.list[4], L.list[5], L.list[6], L.list[7], L.list[8], L.list[9], L.list[10], L.list[11], L.list[12],
                     L.list[13], L.list[14], L.list[15], L.list[16], L.list[17], L.count, L.stamp, L.rstamp, L.status, h->d_tr0, h->d_part, h->d_part2, h->d_scalar,
-                    h->d_labels, h->d_labels_prev, h->d_tflags, h->d_tsum, h->d_image, h->d_lut, h->d_lut_new, h->d_prob, h->d_fg, h->d_bg, h->d_tr_in, h->d_eslot, h->d_eval, h->d_erun, h->d_dense, (void*)h->d_dense_planes, L.hshadow[0], L.hshadow[1], h->d_vout, h->d_dt16, h->d_ds16, h->d_hexact, h->d_halo, h->d_xchg[0], h->d_xchg[1], h->d_xchg[2], h->d_xchg[3], h->d_cnt64, h->d_carry[0], h->d_carry[1], h->d_carry_in[0], h->d_carry_in[1]};
+                    h->d_labels, h->d_labels_prev, h->d_tflags, h->d_tsum, h->d_image, h->d_lut, h->d_lut_new, h->d_prob, h->d_fg, h->d_bg, h->d_tr_in, h->d_tw_part, h->d_eslot, h->d_eval, h->d_erun, h->d_dense, (void*)h->d_dense_planes, L.hshadow[0], L.hshadow[1], h->d_vout, h->d_dt16, h->d_ds16, h->d_hexact, h->d_halo, h->d_xchg[0], h->d_xchg[1], h->d_xchg[2], h->d_xchg[3], h->d_cnt64, h->d_carry[0], h->d_carry[1], h->d_carry_in[0], h->d_carry_in[1]};
     for (void* p : ptrs)
         if (p) (void)mgc_dfree(p);
     for (auto& planes : h->dense_extra)
@@ -4457,6 +4465,7 @@ int mgc_set_markers(mgc_handle h, const uint8_t* fg, const uint8_t* bg)
 int mgc_set_tweights_merged(mgc_handle h, const double* tr, double flow_const)
 {
     if (!h || !tr) return MGC_ERR_INVALID;
+    if (h->tw_store) return mgc_fail(h, MGC_ERR_STATE, "mgc_set_tweights_merged: the handle holds the store of mgc_add_tweights (mgc_clear_tweights first)");
     MGC_HIP(h, hipSetDevice(h->device));
     h->flow_const_in = flow_const;
     h->built = h->solved = false;
@@ -4481,6 +4490,7 @@ static int mgc_update_tlinks(mgc_handle h)
     MgcBuildArgs& A = h->build_args; /* (the readers of the cut value and the invariants take the inputs from here too) */
     A.prob = h->d_prob; A.prob_dtype = h->prob_dtype; A.alpha = h->alpha;
     A.fg = h->d_fg; A.bg = h->d_bg;
+    A.tr_in = h->d_tr_in; /* (mgc_edit_tweights can give a built handle its first store) */
     const int grid = L.ntiles < h->grid_cap * 4 ? L.ntiles : h->grid_cap * 4;
     MGC_HIP(h, hipEventRecord(h->ev[0], h->stream));
     /* the counters start from zero as after mgc_build (k_update_tlinks counts the sink tiles) */
@@ -5098,6 +5108,296 @@ int mgc_get_nweight_edit_info(mgc_handle h, int64_t* out4)
     return MGC_OK;
 }
 
+/* ---- dense t-link weight arrays and their edits by list: kernels in mgc_tweight_ops.inl, the list check in mgc_tweight_edit.h ---- */
+
+static int64_t mgc_tw_share_at(mgc_handle h) { return (h->nvox + 1) & ~(int64_t)1; } /* first entry of the share plane: a 16-byte border */
+static size_t mgc_tw_store_bytes(mgc_handle h) { return (size_t)(mgc_tw_share_at(h) + h->nvox) * sizeof(double); }
+static size_t mgc_tw_part_bytes(mgc_handle h) { return (size_t)(mgc_tw_segments(h->nvox) + 1) * sizeof(double); }
+
+/* forgets the explicit t-links of the handle, whichever call gave them (the stream is quiet) */
+static void mgc_tw_drop(mgc_handle h)
+{
+    if (h->d_tr_in) {
+        (void)mgc_dfree(h->d_tr_in);
+        size_t& cap = h->buf_cap[(const void*)&h->d_tr_in];
+        h->device_bytes -= (int64_t)cap;
+        cap = 0;
+        h->d_tr_in = nullptr;
+    }
+    if (h->d_tw_part) { (void)mgc_dfree(h->d_tw_part); h->device_bytes -= (int64_t)mgc_tw_part_bytes(h); h->d_tw_part = nullptr; }
+    h->tw_store = false;
+    h->flow_const_in = 0.0;
+    h->tw_info[0] = h->tw_info[1] = h->tw_info[2] = 0;
+}
+
+/* a zeroed store and its zeroed partials, not yet the handle's (mgc_tw_attach): what fails for want of memory fails before anything changes */
+static hipError_t mgc_tw_alloc(mgc_handle h, double** store, double** part)
+{
+    *store = *part = nullptr;
+    hipError_t e = mgc_dmalloc((void**)store, mgc_tw_store_bytes(h));
+    if (e == hipSuccess) e = mgc_dmalloc((void**)part, mgc_tw_part_bytes(h));
+    if (e == hipSuccess) e = hipMemsetAsync(*store, 0, mgc_tw_store_bytes(h), h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(*part, 0, mgc_tw_part_bytes(h), h->stream);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(h->stream);
+        if (*store) (void)mgc_dfree(*store);
+        if (*part) (void)mgc_dfree(*part);
+        *store = *part = nullptr;
+    }
+    return e;
+}
+
+static void mgc_tw_attach(mgc_handle h, double* store, double* part)
+{
+    h->d_tr_in = store;
+    h->buf_cap[(const void*)&h->d_tr_in] = mgc_tw_store_bytes(h);
+    h->d_tw_part = part;
+    h->device_bytes += (int64_t)(mgc_tw_store_bytes(h) + mgc_tw_part_bytes(h));
+    h->tw_store = true;
+    h->flow_const_in = 0.0;
+}
+
+/* The flow constant of a store: the partials of the nsegs segments d_segs names (NULL: of every segment) are summed again, then the
+ * partials in the fixed order of k_sum_partials.  Waits for the stream. */
+static hipError_t mgc_tw_flow_const(mgc_handle h, double* store, double* part, int64_t nsegs, const int64_t* d_segs, double* total)
+{
+    const int64_t all = mgc_tw_segments(h->nvox);
+    if (!d_segs) nsegs = all;
+    const int64_t wgs = (nsegs + 3) / 4;
+    hipLaunchKernelGGL(k_tw_partials, dim3((unsigned)(wgs < 8192 ? wgs : 8192)), dim3(256), 0, h->stream, (const double*)(store + mgc_tw_share_at(h)), h->nvox, nsegs, d_segs, part);
+    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(MGC_TV), 0, h->stream, (const double*)part, all, part + all);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(h->h_scalar + 5, part + all, sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess) *total = h->h_scalar[5];
+    return e;
+}
+
+/* The caller's two arrays go up into blocks of the pool (tmp[0], tmp[1]: the caller gives them back) and are checked there.
+ * MGC_OK, or the refusal with the blocks given back already. */
+static int mgc_tw_upload_checked(mgc_handle h, const char* what, const void* source, const void* sink, int dtype, void** tmp, double* upload_ms, double* check_ms)
+{
+    typedef std::chrono::steady_clock Clock;
+    auto ms_since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
+    const bool f32 = dtype == MGC_F32;
+    const size_t bytes = (size_t)h->nvox * (f32 ? sizeof(float) : sizeof(double));
+    tmp[0] = tmp[1] = nullptr;
+    auto release = [&]() {
+        (void)hipStreamSynchronize(h->stream);
+        for (int k = 0; k < 2; ++k) { if (tmp[k]) (void)mgc_dfree(tmp[k]); tmp[k] = nullptr; }
+    };
+    auto t0 = Clock::now();
+    hipError_t e = mgc_dmalloc(&tmp[0], bytes);
+    if (e == hipSuccess) e = mgc_dmalloc(&tmp[1], bytes);
+    if (e == hipSuccess) e = mgc_staged_copy(h, tmp[0], const_cast<void*>(source), bytes, true);
+    if (e == hipSuccess) e = mgc_staged_copy(h, tmp[1], const_cast<void*>(sink), bytes, true);
+    if (e != hipSuccess) { release(); MGC_HIP(h, e); }
+    *upload_ms = ms_since(t0);
+    t0 = Clock::now();
+    unsigned long long* const h_first = (unsigned long long*)(h->h_scalar + 7);
+    unsigned long long* const d_first = (unsigned long long*)(h->d_scalar + 7);
+    e = hipMemsetAsync(d_first, 0xff, sizeof(double), h->stream);
+    if (e == hipSuccess) {
+        const int64_t wgs = ((h->nvox + 1) / 2 + 255) / 256;
+        const unsigned grid = (unsigned)(wgs < 4096 ? wgs : 4096);
+        if (f32) hipLaunchKernelGGL((k_tw_check<float>), dim3(grid), dim3(256), 0, h->stream, h->nvox, (const float*)tmp[0], (const float*)tmp[1], d_first);
+        else hipLaunchKernelGGL((k_tw_check<double>), dim3(grid), dim3(256), 0, h->stream, h->nvox, (const double*)tmp[0], (const double*)tmp[1], d_first);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(h_first, d_first, sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { release(); MGC_HIP(h, e); }
+    *check_ms = ms_since(t0);
+    if (*h_first != MGC_TW_NONE) {
+        const int which = (int)(*h_first & 1ull);
+        const int64_t id = (int64_t)(*h_first >> 1);
+        double v = 0.0;
+        float vf = 0.f;
+        if (f32) { e = hipMemcpy(&vf, (const float*)tmp[which] + id, sizeof(float), hipMemcpyDeviceToHost); v = vf; }
+        else e = hipMemcpy(&v, (const double*)tmp[which] + id, sizeof(double), hipMemcpyDeviceToHost);
+        release();
+        MGC_HIP(h, e);
+        return mgc_fail(h, MGC_ERR_INVALID, "%s: %s[%lld] = %g: t-link weights must be finite", what, which ? "sink" : "source", (long long)id, v);
+    }
+    return MGC_OK;
+}
+
+/* k_tw_merge of checked arrays into `store`, then its flow constant from every segment.  Waits for the stream. */
+static hipError_t mgc_tw_merge(mgc_handle h, int dtype, void* const* tmp, double* store, double* part, bool fresh, bool count, double* total, int64_t* changed)
+{
+    unsigned long long* const d_changed = (unsigned long long*)(h->d_scalar + 6);
+    hipError_t e = count ? hipMemsetAsync(d_changed, 0, sizeof(double), h->stream) : hipSuccess;
+    if (e != hipSuccess) return e;
+    const int64_t wgs = ((h->nvox + 1) / 2 + 255) / 256;
+    const unsigned grid = (unsigned)(wgs < 8192 ? wgs : 8192);
+    double* const share = store + mgc_tw_share_at(h);
+    if (dtype == MGC_F32) hipLaunchKernelGGL((k_tw_merge<float>), dim3(grid), dim3(256), 0, h->stream, h->nvox, (const float*)tmp[0], (const float*)tmp[1], store, share, fresh ? 1 : 0, count ? d_changed : nullptr);
+    else hipLaunchKernelGGL((k_tw_merge<double>), dim3(grid), dim3(256), 0, h->stream, h->nvox, (const double*)tmp[0], (const double*)tmp[1], store, share, fresh ? 1 : 0, count ? d_changed : nullptr);
+    e = hipGetLastError();
+    if (e == hipSuccess && count) e = hipMemcpyAsync(h->h_scalar + 6, d_changed, sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = mgc_tw_flow_const(h, store, part, 0, nullptr, total);
+    if (e == hipSuccess && count) *changed = (int64_t)*(const unsigned long long*)(h->h_scalar + 6);
+    return e;
+}
+
+static int mgc_tw_args(mgc_handle h, const char* what, const void* source, const void* sink, int dtype)
+{
+    if (!source || !sink) return mgc_fail(h, MGC_ERR_INVALID, "%s: source / sink NULL", what);
+    if (dtype != MGC_F32 && dtype != MGC_F64) return mgc_fail(h, MGC_ERR_INVALID, "%s: weights must be float32 or float64", what);
+    if (h->d_tr_in && !h->tw_store) return mgc_fail(h, MGC_ERR_STATE, "%s: the handle's explicit t-links came from mgc_set_tweights_merged (mgc_clear_tweights first)", what);
+    return MGC_OK;
+}
+
+int mgc_add_tweights(mgc_handle h, const void* source, const void* sink, int dtype)
+{
+    if (!h) return MGC_ERR_INVALID;
+    if (h->nranks > 1) return mgc_fail(h, MGC_ERR_UNSUPPORTED, "mgc_add_tweights: not on a slab of a multi-GPU volume");
+    { const int rc = mgc_tw_args(h, "mgc_add_tweights", source, sink, dtype); if (rc) return rc; }
+    MGC_HIP(h, hipSetDevice(h->device));
+    typedef std::chrono::steady_clock Clock;
+    void* tmp[2];
+    double upload_ms = 0.0, check_ms = 0.0;
+    { const int rc = mgc_tw_upload_checked(h, "mgc_add_tweights", source, sink, dtype, tmp, &upload_ms, &check_ms); if (rc) return rc; }
+    const auto t0 = Clock::now();
+    double* store = h->d_tr_in;
+    double* part = h->d_tw_part;
+    hipError_t e = hipSuccess;
+    if (!h->tw_store) e = mgc_tw_alloc(h, &store, &part);
+    double total = 0.0;
+    if (e == hipSuccess) {
+        e = mgc_tw_merge(h, dtype, tmp, store, part, false, false, &total, nullptr);
+        if (e != hipSuccess && !h->tw_store) { (void)hipStreamSynchronize(h->stream); (void)mgc_dfree(store); (void)mgc_dfree(part); }
+    }
+    (void)hipStreamSynchronize(h->stream);
+    for (void* p : tmp) (void)mgc_dfree(p); /* the blocks go back before the call returns */
+    MGC_HIP(h, e);
+    const double accumulate_ms = std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
+    if (!h->tw_store) mgc_tw_attach(h, store, part);
+    h->flow_const_in = total;
+    h->tw_info[0]++;
+    h->built = h->solved = false;
+    /* no error: the note says where the time of this call went (tools/gpu_dense_tweights.py records it) */
+    (void)mgc_fail(h, MGC_OK, "mgc_add_tweights: upload_ms=%.3f check_ms=%.3f accumulate_ms=%.3f", upload_ms, check_ms, accumulate_ms);
+    return MGC_OK;
+}
+
+int mgc_clear_tweights(mgc_handle h)
+{
+    if (!h) return MGC_ERR_INVALID;
+    MGC_HIP(h, hipSetDevice(h->device));
+    MGC_HIP(h, hipStreamSynchronize(h->stream));
+    mgc_tw_drop(h);
+    h->built = h->solved = false;
+    return MGC_OK;
+}
+
+int mgc_update_tweights(mgc_handle h, const void* source, const void* sink, int dtype)
+{
+    if (!h) return MGC_ERR_INVALID;
+    { const int rc = mgc_update_check(h, "mgc_update_tweights"); if (rc) return rc; }
+    { const int rc = mgc_tw_args(h, "mgc_update_tweights", source, sink, dtype); if (rc) return rc; }
+    MGC_HIP(h, hipSetDevice(h->device));
+    MgcRange range_("mgc_update_tweights");
+    void* tmp[2];
+    double upload_ms = 0.0, check_ms = 0.0;
+    { const int rc = mgc_tw_upload_checked(h, "mgc_update_tweights", source, sink, dtype, tmp, &upload_ms, &check_ms); if (rc) return rc; }
+    double* store = h->d_tr_in;
+    double* part = h->d_tw_part;
+    hipError_t e = hipSuccess;
+    if (!h->tw_store) e = mgc_tw_alloc(h, &store, &part);
+    double total = 0.0;
+    int64_t changed = 0;
+    if (e == hipSuccess) {
+        e = mgc_tw_merge(h, dtype, tmp, store, part, true, true, &total, &changed);
+        if (e != hipSuccess && !h->tw_store) { (void)hipStreamSynchronize(h->stream); (void)mgc_dfree(store); (void)mgc_dfree(part); }
+    }
+    (void)hipStreamSynchronize(h->stream);
+    for (void* p : tmp) (void)mgc_dfree(p);
+    MGC_HIP(h, e);
+    if (!h->tw_store) mgc_tw_attach(h, store, part);
+    h->flow_const_in = total;
+    h->tw_info[0] = 1; /* what clear + one mgc_add_tweights leave */
+    h->tw_info[1] = 0;
+    h->tw_info[2] = changed;
+    h->has_prev = false;
+    return mgc_update_tlinks(h);
+}
+
+int mgc_edit_tweights(mgc_handle h, int64_t n, const int64_t* ids, const double* source, const double* sink)
+{
+    if (!h) return MGC_ERR_INVALID;
+    { const int rc = mgc_update_check(h, "mgc_edit_tweights"); if (rc) return rc; }
+    if (h->d_tr_in && !h->tw_store) return mgc_fail(h, MGC_ERR_STATE, "mgc_edit_tweights: the handle's explicit t-links came from mgc_set_tweights_merged (mgc_clear_tweights first)");
+    if (n < 0 || (n > 0 && (!ids || !source || !sink))) return mgc_fail(h, MGC_ERR_INVALID, "mgc_edit_tweights: n = %lld, ids / source / sink NULL", (long long)n);
+    if (n == 0) return MGC_OK;
+    /* every check before the first write: a refused call leaves the handle as it was */
+    MgcTweightList list;
+    {
+        char msg[256];
+        int64_t bad = -1;
+        if (mgc_tweight_list_check(h->nvox, n, ids, source, sink, &list, &bad, msg, sizeof(msg)) != MGC_TW_LIST_OK)
+            return mgc_fail(h, MGC_ERR_INVALID, "mgc_edit_tweights: %s", msg);
+    }
+    if (list.sorted_copy) { ids = list.ids.data(); source = list.source.data(); sink = list.sink.data(); }
+    std::vector<int64_t> segs;
+    mgc_tweight_list_segments(n, ids, &segs);
+    MGC_HIP(h, hipSetDevice(h->device));
+    MgcRange range_("mgc_edit_tweights");
+    /* what can fail for want of memory comes first */
+    if (h->solved && !h->d_labels_prev) { const int rc = mgc_alloc(h, &h->d_labels_prev, h->nvox); if (rc) return rc; }
+    const size_t list_bytes = (size_t)n * sizeof(int64_t), seg_bytes = segs.size() * sizeof(int64_t);
+    void* d_list = nullptr; void* own = nullptr;
+    { const int rc = mgc_call_scratch(h, 0, 3 * list_bytes + seg_bytes, &d_list, &own); if (rc) return rc; }
+    if (!h->tw_store) {
+        double* store = nullptr; double* part = nullptr;
+        const hipError_t e = mgc_tw_alloc(h, &store, &part);
+        if (e != hipSuccess) { (void)mgc_dfree(own); MGC_HIP(h, e); }
+        mgc_tw_attach(h, store, part);
+    }
+    if (h->solved) { /* the labels of the finished solve change hands, as in mgc_edit_markers */
+        std::swap(h->d_labels, h->d_labels_prev);
+        h->has_prev = true;
+    }
+    char* const base = (char*)d_list;
+    unsigned long long* const d_changed = (unsigned long long*)(h->d_scalar + 6);
+    double* const share = h->d_tr_in + mgc_tw_share_at(h);
+    hipError_t e = hipMemcpyAsync(base, ids, list_bytes, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(base + list_bytes, source, list_bytes, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(base + 2 * list_bytes, sink, list_bytes, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(base + 3 * list_bytes, segs.data(), seg_bytes, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_changed, 0, sizeof(double), h->stream);
+    if (e == hipSuccess) e = hipEventRecord(h->ev[2], h->stream);
+    if (e == hipSuccess) {
+        const int64_t wgs = (n + 255) / 256;
+        hipLaunchKernelGGL(k_tw_scatter, dim3((unsigned)(wgs < 4096 ? wgs : 4096)), dim3(256), 0, h->stream, n, h->nvox, (const int64_t*)base,
+                           (const double*)(base + list_bytes), (const double*)(base + 2 * list_bytes), h->d_tr_in, share, d_changed);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(h->h_scalar + 6, d_changed, sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    double total = 0.0;
+    if (e == hipSuccess) e = mgc_tw_flow_const(h, h->d_tr_in, h->d_tw_part, (int64_t)segs.size(), (const int64_t*)(base + 3 * list_bytes), &total);
+    if (e == hipSuccess) e = hipEventRecord(h->ev[3], h->stream);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(h->stream); (void)mgc_dfree(own); MGC_HIP(h, e); }
+    h->flow_const_in = total;
+    h->tw_info[1] = n;
+    h->tw_info[2] = (int64_t)*(const unsigned long long*)(h->h_scalar + 6);
+    int rc = mgc_update_tlinks(h); /* (waits for the stream: the list is consumed) */
+    (void)mgc_dfree(own);
+    if (rc) return rc;
+    float ms = 0.f;
+    MGC_HIP(h, hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
+    h->stats.update_ms += ms;
+    return MGC_OK;
+}
+
+int mgc_get_tweight_edit_info(mgc_handle h, int64_t* out4)
+{
+    if (!h || !out4) return MGC_ERR_INVALID;
+    out4[0] = h->tw_store ? 1 : 0;
+    for (int k = 0; k < 3; ++k) out4[1 + k] = h->tw_info[k];
+    return MGC_OK;
+}
+
 /* the boundary term's part of MgcBuildArgs from what the handle holds now: image, term, sigma, spacing, table (mgc_build, mgc_update_boundary) */
 static int mgc_boundary_args(mgc_handle h, MgcBuildArgs& A)
 {
@@ -5404,7 +5704,12 @@ int mgc_maxflow(mgc_handle h, double* flow)
              * Only where the caller set neither knob. */
             MgcSolveParams P = h->params;
             const int sparse_before = h->sweeps_sparse26;
-            if (h->prepush && h->d_prob) {
+            /* A regional term given as dense t-link arrays (mgc_add_tweights) is such a graph too: on the full neighbourhood k_build pre-pushes
+             * by the t-links a tile holds, wherever they came from.  Config 3 with its map as dense t-links, 512^3: 45.1 ms of solve with the
+             * general defaults against 21.3 ms for the map handle (profiles/dense_tweights.jsonl).  A store that only list edits filled
+             * (no dense call) is a markers graph with a few t-links and keeps the general defaults. */
+            const bool dense_regional = h->tw_store && h->tw_info[0] > 0;
+            if (h->prepush && (h->d_prob || dense_regional)) {
                 if (!h->rounds_set) P.rounds_per_relabel = 3;
                 if (!h->sparse26_set) h->sweeps_sparse26 = P.max_sweeps;
                 /* ... and what is left to discharge are the heavy tiles (every voxel holds excess): there the one-wave-per-tile kernel,

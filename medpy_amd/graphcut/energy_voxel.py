@@ -17,7 +17,7 @@ __all__ = [
     "boundary_maximum_exponential", "boundary_difference_exponential",
     "boundary_maximum_division", "boundary_difference_division",
     "boundary_maximum_power", "boundary_difference_power",
-    "boundary_precomputed",
+    "boundary_precomputed", "regional_precomputed",
 ]
 
 
@@ -112,3 +112,13 @@ def boundary_precomputed(graph, xxx_todo_changeme9):
             graph.set_nweights_dense(axis, w[0], w[1])
         else:
             graph.set_nweights_dense(axis, w)
+
+
+def regional_precomputed(graph, xxx_todo_changeme10):
+    """Regional term from t-link weights the caller has evaluated already (extension; no reference counterpart): negative
+    log-likelihoods of a mixture model or a histogram, the output of a network.  ``weights_source[p]`` / ``weights_sink[p]``
+    are the capacities of the links source -> p and p -> sink, arrays of the volume's shape.  They reach the tile solver as whole
+    arrays (``GCGraph.set_tweights_dense``), not voxel by voxel."""
+    (weights_source, weights_sink) = xxx_todo_changeme10
+    _need_facade(graph)
+    graph.set_tweights_dense(weights_source, weights_sink)

@@ -222,6 +222,69 @@ def normalise_nweight_edit(nodes_from, nodes_to, weight_there, weight_back=None)
     return out[0], out[1], out[2], (out[3] if weight_back is not None else None)
 
 
+def normalise_tweight_edit(shape, nodes, weights_source, weights_sink):
+    """What ``VoxelGraph.edit_tweights`` sends (mgc_edit_tweights, include/medpy_hip.h): ``(ids, source, sink)`` -- C-contiguous 1-D
+    arrays of one length, ids int64 (flat, C order), weights float64.
+
+    ``nodes``: a flat node id, a 1-D integer array of them, or a tuple of per-axis index arrays as ``numpy.nonzero`` returns
+    (one per axis of ``shape``).  ``weights_source`` / ``weights_sink``: scalars or 1-D arrays; scalars are broadcast to the
+    length of the arrays (all scalars: one voxel).  Pure host code; the library checks the range of flat ids, the weights and
+    repeated ids.  ValueError for ids that are not whole numbers, a tuple of the wrong length or with an index outside the
+    volume, arrays of more than one axis and arrays of different lengths."""
+    shape = tuple(int(v) for v in shape)
+    if isinstance(nodes, tuple):
+        if len(nodes) != len(shape):
+            raise ValueError("edit_tweights: %d index arrays for a volume of %d axes" % (len(nodes), len(shape)))
+        axes = [numpy.atleast_1d(numpy.asarray(a)) for a in nodes]
+        if any(a.size and a.dtype.kind not in "iu" for a in axes):
+            raise ValueError("edit_tweights: index arrays must hold integers")
+        if len({a.shape for a in axes}) != 1 or axes[0].ndim != 1:
+            raise ValueError("edit_tweights: index arrays must be 1-D and of one length")
+        if axes[0].size and any(int(a.min()) < 0 or int(a.max()) >= n for a, n in zip(axes, shape)):
+            raise ValueError("edit_tweights: index outside the volume of shape %s" % (shape,))
+        ids = numpy.ravel_multi_index(tuple(a.astype(numpy.int64) for a in axes), shape) if axes[0].size else numpy.empty(0, dtype=numpy.int64)
+    else:
+        ids = numpy.asarray(nodes)
+        if ids.ndim > 1:
+            raise ValueError("edit_tweights: nodes must be a scalar, a 1-D array or a tuple of per-axis index arrays, not of shape %s" % (ids.shape,))
+        if ids.size and ids.dtype.kind not in "iu":
+            raise ValueError("edit_tweights: nodes must hold integers, not %s" % ids.dtype)
+    arrays = [ids, numpy.asarray(weights_source), numpy.asarray(weights_sink)]
+    for a, name in zip(arrays[1:], ("weights_source", "weights_sink")):
+        if a.ndim > 1:
+            raise ValueError("edit_tweights: %s must be a scalar or a 1-D array, not of shape %s" % (name, a.shape))
+        if a.dtype.kind not in "iufb":
+            raise ValueError("edit_tweights: %s of dtype %s" % (name, a.dtype))
+    lengths = {a.shape[0] for a in arrays if a.ndim == 1}
+    if len(lengths) > 1:
+        raise ValueError("edit_tweights: arrays of different lengths %s" % sorted(lengths))
+    n = lengths.pop() if lengths else 1
+    out = [numpy.ascontiguousarray(numpy.broadcast_to(a, (n,)), dtype=numpy.int64 if k == 0 else numpy.float64) for k, a in enumerate(arrays)]
+    return out[0], out[1], out[2]
+
+
+def _dense_tweight_arrays(shape, weights_source, weights_sink):
+    """the two arrays of ``set_tweights_dense`` in the volume's shape and one dtype: float32 / float64 as they are, anything else --
+    and two arrays of different dtypes -- as float64; arrays of the volume's shape or flat arrays of one entry per node"""
+    shape = tuple(int(v) for v in shape)
+    nodes = 1
+    for v in shape:
+        nodes *= v
+    out = []
+    for w, what in ((weights_source, "weights_source"), (weights_sink, "weights_sink")):
+        w = numpy.asarray(w)
+        if w.dtype.kind not in "iufb":
+            raise ValueError("%s: weights of dtype %s" % (what, w.dtype))
+        if w.shape != shape and w.shape != (nodes,):
+            raise ValueError("%s of shape %s on a graph of shape %s (%d nodes)" % (what, w.shape, shape, nodes))
+        if w.dtype not in (numpy.float32, numpy.float64):
+            w = w.astype(numpy.float64)
+        out.append(w.reshape(shape))
+    if out[0].dtype != out[1].dtype:
+        out = [w.astype(numpy.float64) for w in out]
+    return numpy.ascontiguousarray(out[0]), numpy.ascontiguousarray(out[1])
+
+
 def pad_skeleton_weights(shape, axis, weights):
     """The per-axis weight array of the reference's ``__skeleton_base`` (energy_voxel.py:644-658: extent - 1 along ``axis``, entry p =
     the pair (p, p + e_axis)) as an array of the full ``shape``: the same entries, and one more slice along ``axis`` that holds
@@ -294,6 +357,8 @@ class VoxelGraph(object):
     """
 
     termtype = termtype
+
+    _tweights_merged = False   # the explicit t-links came from set_tweight calls merged on the host (_set_tweights_merged)
 
     def __init__(self, shape, device=0, connectivity=None):
         lib = _lib.load()
@@ -484,6 +549,57 @@ class VoxelGraph(object):
     def _set_tweights_merged(self, tr, flow_const):
         tr = numpy.ascontiguousarray(tr, dtype=numpy.float64)
         self._call("mgc_set_tweights_merged", _lib.ptr(tr), float(flow_const))
+        self._tweights_merged = True
+
+    # -- dense t-link weight arrays
+    def _add_tweights(self, weights_source, weights_sink):
+        """mgc_add_tweights: one ``add_tweights(source[p], sink[p])`` per voxel on the graph's explicit t-links; arrays of the
+        volume's shape (or flat).  float32 / float64 go up as they are, anything else as float64."""
+        source, sink = _dense_tweight_arrays(self._shape, weights_source, weights_sink)
+        self._labels = None
+        self._call("mgc_add_tweights", _lib.ptr(source), _lib.ptr(sink), _lib.DTYPE_IDS[source.dtype])
+
+    def _clear_tweights(self):
+        """mgc_clear_tweights: forget the explicit t-links (and free their store); the graph is unbuilt afterwards"""
+        self._labels = None
+        self._call("mgc_clear_tweights")
+        self._tweights_merged = False
+
+    def tweight_edit_info(self):
+        """is the store of dense t-link arrays held, dense calls accumulated in it, and of the last ``edit_tweights`` /
+        ``update_tweights_dense``: entries of the list, voxels whose explicit t-link changed bitwise (mgc_get_tweight_edit_info)"""
+        out = numpy.zeros(4, dtype=numpy.int64)
+        self._call("mgc_get_tweight_edit_info", _lib.ptr(out))
+        return dict(zip(("store_held", "dense_calls", "list_entries", "voxels_changed"), out.tolist()))
+
+    def _refuse_host_merged(self, what):
+        if self._tweights_merged:
+            raise NotImplementedError("medpy_amd: %s on a graph whose explicit t-links were merged on the host (set_tweight calls): "
+                                      "the per-voxel shares of its flow constant are not known; build it from set_tweights_dense alone" % what)
+
+    def update_tweights_dense(self, weights_source, weights_sink):
+        """Replace the explicit t-links by those of ONE ``set_tweights_dense(weights_source, weights_sink)`` -- whatever dense calls
+        the graph was built from -- and keep the residual graph: the next ``maxflow()`` is a warm solve with the labels and the flow
+        of a graph built from the new arrays (regional probability map and markers on top, as built).  MedpyHipError (ERR_INVALID)
+        names the first entry that is not finite; the graph is then as it was."""
+        self._refuse_host_merged("update_tweights_dense")
+        source, sink = _dense_tweight_arrays(self._shape, weights_source, weights_sink)
+        self._labels = None
+        self._call("mgc_update_tweights", _lib.ptr(source), _lib.ptr(sink), _lib.DTYPE_IDS[source.dtype])
+
+    def edit_tweights(self, nodes, weights_source, weights_sink):
+        """Set the explicit t-links of the built graph by voxel list (REPLACE, not add): afterwards voxel ``nodes[k]`` holds what
+        one ``set_tweight(nodes[k], weights_source[k], weights_sink[k])`` leaves on a graph without explicit t-links; the regional
+        probability map and the markers stay on top.  ``nodes``: flat ids or a tuple of per-axis index arrays; weights: scalars or
+        1-D arrays (``normalise_tweight_edit``).  The next ``maxflow()`` is a warm solve with the labels and the flow of a graph
+        built from the edited t-links; the edits stay with the graph, a rebuild sees them.  If the graph holds a finished cut its
+        labels are kept on the device, so ``changed_labels()`` and ``labels(out=previous)`` work afterwards.  MedpyHipError
+        (ERR_INVALID) names the first offending entry (bad id, weight that is not finite, id twice); the graph is then as it was."""
+        self._refuse_host_merged("edit_tweights")
+        ids, source, sink = normalise_tweight_edit(self._shape, nodes, weights_source, weights_sink)
+        self._call("mgc_edit_tweights", ids.size, _lib.ptr(ids), _lib.ptr(source), _lib.ptr(sink))
+        if ids.size:
+            self._labels = None
 
     def _add_nweights(self, offset, there, back=None):
         """mgc_add_nweights: ``there[p]`` is added to the arc p -> p + offset, ``back[p]`` (None: ``there[p]``) to the arc
@@ -717,6 +833,16 @@ class SparseGraph(object):
         """Edits by list exist for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
         raise NotImplementedError("medpy_amd: edit_nweights is implemented for the voxel lattice solver (1-D..3-D volumes, "
                                   "VoxelGraph) only; this graph went to the sparse-graph solver: build it again from the new inputs")
+
+    def update_tweights_dense(self, weights_source, weights_sink):
+        """Whole t-link arrays exist for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only; here: ``update_tweights``."""
+        raise NotImplementedError("medpy_amd: update_tweights_dense is implemented for the voxel lattice solver (1-D..3-D volumes, "
+                                  "VoxelGraph) only; this graph went to the sparse-graph solver: update_tweights(nodes, tr)")
+
+    def edit_tweights(self, nodes, weights_source, weights_sink):
+        """Edits by list exist for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only; here: ``update_tweights``."""
+        raise NotImplementedError("medpy_amd: edit_tweights is implemented for the voxel lattice solver (1-D..3-D volumes, "
+                                  "VoxelGraph) only; this graph went to the sparse-graph solver: update_tweights(nodes, tr)")
 
     def clear_nweight_edits(self):
         """Edits by list exist for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
@@ -1296,6 +1422,14 @@ class EmbeddedLatticeGraph(object):
         raise NotImplementedError("medpy_amd: edit_nweights is not implemented for a graph whose boundary image has another shape "
                                   "than its markers (EmbeddedLatticeGraph): build it again with graph_from_voxels")
 
+    def update_tweights_dense(self, weights_source, weights_sink):
+        raise NotImplementedError("medpy_amd: update_tweights_dense is not implemented for a graph whose boundary image has another "
+                                  "shape than its markers (EmbeddedLatticeGraph): build it again with graph_from_voxels")
+
+    def edit_tweights(self, nodes, weights_source, weights_sink):
+        raise NotImplementedError("medpy_amd: edit_tweights is not implemented for a graph whose boundary image has another shape "
+                                  "than its markers (EmbeddedLatticeGraph): build it again with graph_from_voxels")
+
     def clear_nweight_edits(self):
         raise NotImplementedError("medpy_amd: clear_nweight_edits is not implemented for a graph whose boundary image has another "
                                   "shape than its markers (EmbeddedLatticeGraph): build it again with graph_from_voxels")
@@ -1423,6 +1557,7 @@ class GCGraph(object):
         self.__edge_i, self.__edge_j, self.__edge_w, self.__edge_r = [], [], [], []
         self.__dense = []  # (offset, there, back or None): whole n-link weight arrays, in call order (set_nweights_dense)
         self.__tr = None  # merged explicit t-links (graph.h:416-425 applied call by call)
+        self.__tdense = []  # (source, sink): whole t-link weight arrays, in call order (set_tweights_dense), while no per-node t-weight exists
         self.__flow_const = 0.0
         self.__graph = None
         self.__lattice_shape = None  # set when the boundary image has another shape than the markers
@@ -1438,7 +1573,7 @@ class GCGraph(object):
             # isolated.  Too many ids -> the same ValueError GCGraph.set_nweight raises (graph.py:418-425).
             if image.size > self.__nodes:
                 raise ValueError("Invalid node id (node_to) of {}. Valid values are 0 to {}.".format(image.size - 1, self.__nodes - 1))
-            if self.__regional is not None or self.__tr is not None or self.__edge_i or self.__dense:
+            if self.__regional is not None or self.__tr is not None or self.__tdense or self.__edge_i or self.__dense:
                 raise NotImplementedError("medpy_amd: a boundary image of another shape cannot be combined with other terms")
             self.__lattice_shape = image.shape
         if self.__boundary is not None:
@@ -1457,6 +1592,7 @@ class GCGraph(object):
             return
         if nodes.max() >= self.__nodes or nodes.min() < 0:
             raise ValueError("Invalid node id of {} or {}. Valid values are 0 to {}.".format(nodes.max(), nodes.min(), self.__nodes - 1))
+        self.__merge_dense_tweights()
         if self.__tr is None:
             self.__tr = numpy.zeros(self.__nodes, dtype=numpy.float64)
         self.__flow_const = merge_tweights_into(self.__tr, self.__flow_const, nodes, weights_source, weights_sink)
@@ -1565,6 +1701,7 @@ class GCGraph(object):
     def set_tweight(self, node, weight_source, weight_sink):
         if node >= self.__nodes or node < 0:
             raise ValueError("Invalid node id of {}. Valid values are 0 to {}.".format(node, self.__nodes - 1))
+        self.__merge_dense_tweights()
         if self.__tr is None:
             self.__tr = numpy.zeros(self.__nodes, dtype=numpy.float64)
         # Graph::add_tweights, graph.h:416-425, call by call
@@ -1576,6 +1713,32 @@ class GCGraph(object):
             ck -= delta
         self.__flow_const += cs if cs < ck else ck
         self.__tr[node] = cs - ck
+
+    def set_tweights_dense(self, weights_source, weights_sink):
+        """Whole t-link weight arrays at once: the call a plug-in regional term makes instead of one ``set_tweight`` per voxel
+        (extension; the reference has no bulk form).  Voxel p gets ``set_tweight(p, weights_source[p], weights_sink[p])``, with
+        the semantics of ``Graph::add_tweights``: repeated calls accumulate in call order, negative weights are allowed.  Arrays
+        of the volume's shape or flat arrays of one entry per node; float32 / float64 are used as they are (float32 is widened,
+        which is exact), anything else -- and two arrays of different dtypes -- as float64.  On a graph of the tile solver whose
+        explicit t-links are nothing but such calls the arrays go to the device as they are (mgc_add_tweights) and are checked
+        there when the graph is built: every entry must be finite (``MedpyHipError``).  Call order against ``set_tweight`` is
+        kept: a call made when per-node t-weights exist is merged into them at once, and the first ``set_tweight`` after such
+        calls merges them first -- as are the calls of graphs that go to the sparse-graph solver.  ValueError for a wrong shape
+        or dtype, before anything is recorded."""
+        source, sink = _dense_tweight_arrays(self.__shape, weights_source, weights_sink)
+        if self.__graph is not None:
+            raise NotImplementedError("medpy_amd: the graph is built already: VoxelGraph.update_tweights_dense / edit_tweights change its t-links")
+        if self.__tr is not None:   # per-node t-weights exist: this call comes after them
+            self.merge_tweights(numpy.arange(self.__nodes), source.ravel(), sink.ravel())
+        else:
+            self.__tdense.append((source, sink))
+
+    def __merge_dense_tweights(self):
+        """the recorded dense calls, merged on the host in call order (a per-node t-weight follows, or the graph goes to a solver
+        that takes one merged vector)"""
+        calls, self.__tdense = self.__tdense, []
+        for source, sink in calls:
+            self.merge_tweights(numpy.arange(self.__nodes), source.ravel(), sink.ravel())
 
     def set_tweights(self, tweights):
         for node, weight in list(tweights.items()):
@@ -1611,6 +1774,8 @@ class GCGraph(object):
             self.__general = True  # a plug-in term added an edge between voxels that are not neighbours
         if self.__graph is None and self.__dense and (self.__general or self.__lattice_shape is not None):
             raise NotImplementedError("medpy_amd: dense n-link weight arrays on a graph that goes to the sparse-graph solver")
+        if self.__graph is None and self.__tdense and (self.__general or self.__lattice_shape is not None):
+            self.__merge_dense_tweights()   # (these solvers take one merged vector)
         if self.__graph is None and self.__general:
             self.__graph = self.__sparse_graph()
         if self.__graph is None and self.__lattice_shape is not None:
@@ -1624,6 +1789,8 @@ class GCGraph(object):
                 g._set_regional(*self.__regional)
             if self.__tr is not None:
                 g._set_tweights_merged(self.__tr, self.__flow_const)
+            for source, sink in self.__tdense:   # (nothing but dense calls: __tr is None)
+                g._add_tweights(source, sink)
             if self.__fg is not None or self.__bg is not None:
                 g._set_markers(None if self.__fg is None else self.__fg, None if self.__bg is None else self.__bg)
             for off, there, back in self.__dense:   # (after the boundary term, before the explicit edges: the order mgc_build applies them in)
