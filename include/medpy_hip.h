@@ -351,6 +351,27 @@ int mgc_maxflow(mgc_handle h, double* flow);
 /* Replaces the per-voxel what_segment loop of bin/medpy_graphcut_voxel.py:177-181:
  * out[i] = 0 if SINK == what_segment(i) else 1. */
 int mgc_labels(mgc_handle h, uint8_t* out);
+
+/* The other side of the answer.  mgc_labels reports R_t, the voxels that can reach the sink in the residual graph of the
+ * maximum flow (out = 0).  mgc_cut_sets computes, on the device, R_s = the voxels the source can reach in that residual graph --
+ * the source side of the SMALLEST minimum cut, where mgc_labels' 1s are the source side of the largest -- and the AMBIGUITY SET
+ * V \ (R_s u R_t): the voxels that some minimum cut puts on the source side and another on the sink side.  The minimum cut is unique
+ * iff that set is empty.  from_source[i] / ambiguous[i] = 0 / 1 per voxel in C order; either pointer may be NULL (both: only the
+ * counts are computed, nothing of the size of the volume comes down).  The sets are those of the handle's own residual graph with an
+ * arc open where its residual capacity is > 0, no tolerance: exact on inputs whose arithmetic is exact (small integers), and on
+ * floating-point inputs as fine-grained as the solve's own rounding.
+ *   Valid on a single handle whose last mgc_maxflow converged, with no update or edit since (cold and warm solves, either
+ * neighbourhood, whatever the capacities came from).  MGC_ERR_STATE before mgc_build, before mgc_maxflow, after an update or edit
+ * that has not been solved, after MGC_ERR_NOT_CONVERGED and after mgc_finish; MGC_ERR_UNSUPPORTED on a slab handle; both before
+ * anything is written.  A call leaves labels, label snapshot (mgc_labels_delta), residual state, statistics and launch counts of the
+ * solve as they were; its mark planes come from the library's pool and go back, device_bytes is the same before and after.
+ *   mgc_get_cut_sets_info, of the last mgc_cut_sets: out8 = {voxels from_source, voxels to_sink, voxels ambiguous, flood passes that
+ * had tiles to visit, tile visits, tiles seeded (they hold excess), tiles skipped unread as wholly on the sink side, 0};
+ * *source_cut = the capacity of the cut (R_s | V \ R_s), flow constant included -- a second minimum cut, so the value
+ * mgc_maxflow returned (bit for bit where the arithmetic is exact, else up to the order of summation).  Either pointer may be NULL.
+ * After a mgc_cut_sets that went through, mgc_last_error holds a note of where its time went (device_ms, download_ms). */
+int mgc_cut_sets(mgc_handle h, uint8_t* from_source, uint8_t* ambiguous);
+int mgc_get_cut_sets_info(mgc_handle h, int64_t* out8, double* source_cut);
 int mgc_what_segment(mgc_handle h, int64_t i, int* segment); /* Graph::what_segment, graph.h:561-571 */
 
 int mgc_get_node_num(mgc_handle h, int64_t* n);

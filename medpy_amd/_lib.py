@@ -157,6 +157,8 @@ SIGNATURES = {
     "mgc_get_edge": (_INT, [_VP, _I64, _I64, C.POINTER(_DBL)]),
     "mgc_maxflow": (_INT, [_VP, C.POINTER(_DBL)]),
     "mgc_labels": (_INT, [_VP, _VP]),
+    "mgc_cut_sets": (_INT, [_VP, _VP, _VP]),
+    "mgc_get_cut_sets_info": (_INT, [_VP, _VP, C.POINTER(_DBL)]),
     "mgc_what_segment": (_INT, [_VP, _I64, C.POINTER(_INT)]),
     "mgc_get_node_num": (_INT, [_VP, C.POINTER(_I64)]),
     "mgc_set_param": (_INT, [_VP, C.c_char_p, _I64]),

@@ -2871,6 +2871,8 @@ struct mgc_graph {
     uint32_t timing_offset = 0; /* which residue of the stride is timed rotates from solve to solve: the launches of a solve have a shape (the flood grows, the
                                    leak shrinks), and a fixed residue samples the same few launches every time -- at stride 7 that read 8 % low on the headline
                                    volume; over seven steps every launch is timed once */
+    bool converged = false;    /* `solved` was set by an mgc_maxflow whose schedule ended on "no active tile" (mgc_finish cannot know): what mgc_cut_sets asks for */
+    int64_t cut_info[8] = {0, 0, 0, 0, 0, 0, 0, 0}; double cut_source = 0.0; bool cut_info_valid = false; /* of the last mgc_cut_sets (mgc_get_cut_sets_info) */
 };
 
 static int mgc_fail(mgc_handle h, int code, const char* fmt, ...)
@@ -5764,6 +5766,7 @@ int mgc_maxflow(mgc_handle h, double* flow)
         h->stats.phases = st.phases;
         h->flow = h->flow_const + h->h_scalar[1];
         h->solved = true;
+        h->converged = true;
         h->labels_on_host = false;
     }
     if (flow) *flow = h->flow;
@@ -5801,6 +5804,7 @@ int mgc_finish(mgc_handle h, double* flow_partial)
     }
     h->flow = h->flow_const + h->h_scalar[1];
     h->solved = true;
+    h->converged = false; /* (driven launch by launch, or a slab: whether the schedule ended is the caller's knowledge) */
     h->labels_on_host = false;
     if (flow_partial) *flow_partial = h->flow;
     return MGC_OK;
@@ -5812,6 +5816,129 @@ int mgc_labels(mgc_handle h, uint8_t* out)
     if (!h->solved) return mgc_fail(h, MGC_ERR_STATE, "mgc_labels before mgc_maxflow");
     MGC_HIP(h, hipSetDevice(h->device));
     MGC_HIP(h, mgc_staged_copy(h, h->d_labels, out, (size_t)h->nvox, false));
+    return MGC_OK;
+}
+
+} /* extern "C" */
+
+/* (included here, behind every other kernel of the file: the kernels of the solve keep their places in the code object) */
+#include "mgc_reach_ops.inl"
+
+/* mgc_cut_sets on the kernels of either neighbourhood (mgc_reach_ops.inl).  Everything the flood writes is its own: the mark plane, the
+ * stamps, the C-order planes and the count block come from the pool and go back; of the handle it uses the two relabel lists with
+ * their counters (empty between two solves, cleared again on the way out), the counter look of the schedule (read_counts), and the
+ * scratch of the cut value (d_part, d_part2, one slot of d_scalar).  Labels, label summaries, snapshot and residual state are read only. */
+template <class Dev>
+static int mgc_cut_sets_on(mgc_handle h, const MgcLayout lay, uint8_t* from_source, uint8_t* ambiguous)
+{
+    MgcRange range_("mgc_cut_sets");
+    MgcLattice& L = h->L;
+    const size_t ntv = (size_t)L.ntiles * MGC_TV, nvox8 = ((size_t)h->nvox + 7) & ~(size_t)7;
+    uint8_t *marks = nullptr, *d_fs = nullptr, *d_amb = nullptr;
+    uint32_t* stamp = nullptr;
+    int32_t* cnt3 = nullptr;
+    unsigned long long* info = nullptr;
+    hipError_t e = mgc_dmalloc((void**)&marks, ntv);
+    if (e == hipSuccess) e = mgc_dmalloc((void**)&d_fs, nvox8);
+    if (e == hipSuccess && ambiguous) e = mgc_dmalloc((void**)&d_amb, nvox8);
+    if (e == hipSuccess) e = mgc_dmalloc((void**)&stamp, (size_t)L.ntiles * sizeof(uint32_t));
+    if (e == hipSuccess) e = mgc_dmalloc((void**)&cnt3, (size_t)L.ntiles * 3 * sizeof(int32_t));
+    if (e == hipSuccess) e = mgc_dmalloc((void**)&info, 8 * sizeof(unsigned long long));
+    auto release = [&]() {
+        for (void* p : {(void*)marks, (void*)d_fs, (void*)d_amb, (void*)stamp, (void*)cnt3, (void*)info}) (void)mgc_dfree(p);
+    };
+    unsigned long long h_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    typedef std::chrono::steady_clock Clock;
+    const auto t0 = Clock::now();
+    Dev dev;
+    dev.h = h;
+    const bool timing = h->timing;
+    h->timing = false; /* (the event pairs of a solve's launches are not for these) */
+    const int lists[2] = {lay.rl_base, lay.rl_base + 1};
+    if (e == hipSuccess) e = hipMemsetAsync(marks, 0, ntv, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(stamp, 0, (size_t)L.ntiles * sizeof(uint32_t), h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(info, 0, 8 * sizeof(unsigned long long), h->stream);
+    if (e == hipSuccess) {
+        dev.zero_count(lists[0]);
+        dev.zero_count(lists[1]);
+        dev.flush_zero();
+        /* the label summaries are those of the labels on the handle where the read-out of the solve wrote them (k_labels8: rows of whole
+         * runs of eight); elsewhere the seed filter reads the labels of a tile itself */
+        const uint8_t* tsum = L.dx % 8 == 0 ? (const uint8_t*)h->d_tsum : (const uint8_t*)nullptr;
+        const int wgs = (L.ntiles + 3) / 4;
+        hipLaunchKernelGGL(k_reach_seed, dim3(wgs < 4096 ? wgs : 4096), dim3(256), 0, h->stream, L, tsum, marks, lists[0], lists[0], info);
+        dev.check(hipGetLastError());
+        /* passes in stretches of relabel_batch between two looks at the length of the list the next pass would consume */
+        const int batch = h->params.relabel_batch > 0 ? h->params.relabel_batch : 8;
+        int cnt[MGC_NCOUNT];
+        uint32_t epoch = 0;
+        for (int k = 0;;) {
+            for (int b = 0; b < batch; ++b, ++k) {
+                const int cur = lists[k & 1], nxt = lists[(k + 1) & 1];
+                dev.zero_count(nxt);
+                dev.flush_zero();
+                ++epoch;
+                if (L.ndir == 6) hipLaunchKernelGGL(k_reach_flood<6>, dim3(dev.grid(L.ntiles)), dim3(MGC_TV), 0, h->stream, L, marks, stamp, cur, cur, epoch, nxt, info);
+                else hipLaunchKernelGGL(k_reach_flood<26>, dim3(dev.grid(L.ntiles)), dim3(MGC_TV), 0, h->stream, L, marks, stamp, cur, cur, epoch, nxt, info);
+                dev.check(hipGetLastError());
+            }
+            dev.read_counts(cnt);
+            if (cnt[lists[k & 1]] == 0 || dev.first_error != hipSuccess) break; /* the last pass queued nobody: fixpoint */
+        }
+        dev.zero_count(lists[0]);
+        dev.zero_count(lists[1]);
+        dev.flush_zero();
+        const int wr = (L.ntiles + 3) / 4;
+        hipLaunchKernelGGL(k_reach_readout, dim3(wr < 4096 ? wr : 4096), dim3(256), 0, h->stream, L, (const uint8_t*)marks, d_fs, d_amb, cnt3);
+        hipLaunchKernelGGL(k_reach_sum, dim3(1), dim3(MGC_TV), 0, h->stream, (const int32_t*)cnt3, L.ntiles, info);
+        /* the capacity of the cut (R_s | V \ R_s) by the label-driven kernel of the solve's read-out, on the marks instead of the labels */
+        const int grid = L.ntiles < h->grid_cap * 4 ? L.ntiles : h->grid_cap * 4;
+        hipLaunchKernelGGL(k_cut_value26<0>, dim3((grid + 3) / 4 < 8192 ? (grid + 3) / 4 : 8192), dim3(256), 0, h->stream, L, h->build_args, (const double*)h->d_tr0, (const uint8_t*)d_fs, (const uint8_t*)nullptr, h->d_part);
+        mgc_sum_partials(h, (int64_t)L.ntiles, h->d_scalar + 4);
+        dev.check(hipGetLastError());
+        e = dev.first_error;
+    }
+    h->timing = timing;
+    if (e == hipSuccess) e = hipMemcpyAsync(h->h_scalar, h->d_scalar, 8 * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess) e = hipMemcpy(h_info, info, sizeof(h_info), hipMemcpyDeviceToHost);
+    const auto t1 = Clock::now();
+    if (e == hipSuccess && from_source) e = mgc_staged_copy(h, d_fs, from_source, (size_t)h->nvox, false);
+    if (e == hipSuccess && ambiguous) e = mgc_staged_copy(h, d_amb, ambiguous, (size_t)h->nvox, false);
+    release();
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return mgc_fail(h, e == hipErrorOutOfMemory ? MGC_ERR_OOM : MGC_ERR_HIP, "mgc_cut_sets: %s", hipGetErrorString(e));
+    }
+    for (int k = 0; k < 8; ++k) h->cut_info[k] = (int64_t)h_info[k];
+    h->cut_info[7] = 0;
+    h->cut_source = h->flow_const + h->h_scalar[4];
+    h->cut_info_valid = true;
+    /* no error: the note says where the time of this call went (tools/gpu_cut_sets.py records it) */
+    (void)mgc_fail(h, MGC_OK, "mgc_cut_sets: device_ms=%.3f download_ms=%.3f", std::chrono::duration<double, std::milli>(t1 - t0).count(),
+                   std::chrono::duration<double, std::milli>(Clock::now() - t1).count());
+    return MGC_OK;
+}
+
+extern "C" {
+
+int mgc_cut_sets(mgc_handle h, uint8_t* from_source, uint8_t* ambiguous)
+{
+    if (!h) return MGC_ERR_INVALID;
+    if (h->nranks > 1) return mgc_fail(h, MGC_ERR_UNSUPPORTED, "mgc_cut_sets: a slab holds a part of the residual graph only (the flood would have to cross the slab borders)");
+    if (!h->built) return mgc_fail(h, MGC_ERR_STATE, "mgc_cut_sets before mgc_build");
+    if (!h->solved) return mgc_fail(h, MGC_ERR_STATE, "mgc_cut_sets before mgc_maxflow (or after an update or edit that the next mgc_maxflow has yet to solve)");
+    if (!h->converged || h->unconverged) return mgc_fail(h, MGC_ERR_STATE, "mgc_cut_sets: the last mgc_maxflow of this handle did not run to a maximum preflow");
+    MGC_HIP(h, hipSetDevice(h->device));
+    return h->L.ndir == 6 ? mgc_cut_sets_on<HipDev>(h, mgc_layout6(), from_source, ambiguous) : mgc_cut_sets_on<HipDev26>(h, mgc_layout26(), from_source, ambiguous);
+}
+
+int mgc_get_cut_sets_info(mgc_handle h, int64_t* out8, double* source_cut)
+{
+    if (!h) return MGC_ERR_INVALID;
+    if (!h->cut_info_valid) return mgc_fail(h, MGC_ERR_STATE, "mgc_get_cut_sets_info before mgc_cut_sets");
+    if (out8) for (int k = 0; k < 8; ++k) out8[k] = h->cut_info[k];
+    if (source_cut) *source_cut = h->cut_source;
     return MGC_OK;
 }
 

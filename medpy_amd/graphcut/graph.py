@@ -354,6 +354,10 @@ class VoxelGraph(object):
     ``edit_markers(fg, bg, erase)`` edits the masks resident in HBM by lists of voxel ids, ``changed_labels()`` returns the ids
     of the voxels whose label the next ``maxflow()`` changed, ``labels(out=previous)`` applies them to the caller's copy of the
     previous labels, and ``markers()`` reads the resident masks back.
+
+    Is the cut unique?  After ``maxflow()``, ``source_side()`` is the source side of the SMALLEST minimum cut (``labels()`` is that
+    of the largest), ``ambiguous()`` the voxels between the two -- some minimum cut has them on either side -- ``cut_is_unique()``
+    whether there are none, ``cut_sets_info()`` the counts; one forward flood of the residual graph on the device.
     """
 
     termtype = termtype
@@ -679,6 +683,54 @@ class VoxelGraph(object):
             self._labels = out.view(numpy.bool_).reshape(self._shape)   # (the library writes 0 / 1: the bytes ARE the bool array, no second pass over the volume)
         return self._labels
 
+    # -- the other minimum cuts
+    CUT_SETS_INFO_KEYS = ("from_source", "to_sink", "ambiguous", "flood_passes", "tile_visits", "tiles_seeded", "tiles_skipped")
+
+    @property
+    def _labels(self):
+        return self.__dict__.get("_labels_cache")
+
+    @_labels.setter
+    def _labels(self, value):
+        # every build, update and edit drops the cached labels by assigning None: what mgc_cut_sets computed goes with them
+        self.__dict__["_labels_cache"] = value
+        if value is None:
+            self.__dict__["_cut_sets_cache"] = {}
+
+    def _cut_sets(self, want):
+        """one mgc_cut_sets per solve and kind of answer: ``want`` = "source_side", "ambiguous" or "info" (no volume comes down)"""
+        cache = self.__dict__.setdefault("_cut_sets_cache", {})
+        if want not in cache:
+            plane = None if want == "info" else numpy.empty(self._nodes, dtype=numpy.uint8)
+            self._call("mgc_cut_sets", _lib.ptr(plane) if want == "source_side" else None, _lib.ptr(plane) if want == "ambiguous" else None)
+            out = numpy.zeros(8, dtype=numpy.int64)
+            cut = C.c_double(0.0)
+            self._call("mgc_get_cut_sets_info", _lib.ptr(out), C.byref(cut))
+            cache["info"] = dict(zip(self.CUT_SETS_INFO_KEYS, out.tolist()), source_cut=cut.value)
+            if plane is not None:
+                cache[want] = plane.view(numpy.bool_).reshape(self._shape)
+        return cache[want]
+
+    def source_side(self):
+        """bool array of the volume's shape, True on the voxels the SOURCE reaches in the residual graph of the maximum flow: the
+        source side of the smallest minimum cut (``labels()`` is that of the largest).  After ``maxflow()``; MedpyHipError
+        (ERR_STATE) before it and after an update or edit that has not been solved.  Cached until the next update or edit."""
+        return self._cut_sets("source_side")
+
+    def ambiguous(self):
+        """bool array, True on the voxels that are neither reachable from the source nor able to reach the sink: some minimum
+        cut has them on the source side, another on the sink side -- where one more stroke would decide something."""
+        return self._cut_sets("ambiguous")
+
+    def cut_sets_info(self):
+        """dict: voxels ``from_source`` / ``to_sink`` / ``ambiguous``, ``flood_passes``, ``tile_visits``, ``tiles_seeded``,
+        ``tiles_skipped`` of the flood, and ``source_cut``, the capacity of the cut around ``source_side()`` (= ``maxflow()``)"""
+        return dict(self._cut_sets("info"))
+
+    def cut_is_unique(self):
+        """is the minimum cut unique, i.e. the ambiguity set empty?  Counted on the device, no volume is read back."""
+        return self._cut_sets("info")["ambiguous"] == 0
+
     def what_segment(self, i):
         """Graph::what_segment, reference graph.h:561-571."""
         seg = C.c_int(0)
@@ -853,6 +905,27 @@ class SparseGraph(object):
         """Edits by list exist for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
         raise NotImplementedError("medpy_amd: nweight_edit_info is implemented for the voxel lattice solver (1-D..3-D volumes, "
                                   "VoxelGraph) only; this graph went to the sparse-graph solver")
+
+    def _no_cut_sets(self, what):
+        raise NotImplementedError("medpy_amd: %s is implemented for the voxel lattice solver (1-D..3-D volumes, VoxelGraph) only; this "
+                                  "graph went to the sparse-graph solver, which keeps its residual graph as CSR arcs: the forward "
+                                  "flood over tile masks does not apply (labels() is the sink side's complement)" % what)
+
+    def source_side(self):
+        """The source side of the smallest minimum cut exists for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
+        self._no_cut_sets("source_side")
+
+    def ambiguous(self):
+        """The ambiguity set exists for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
+        self._no_cut_sets("ambiguous")
+
+    def cut_is_unique(self):
+        """The ambiguity set exists for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
+        self._no_cut_sets("cut_is_unique")
+
+    def cut_sets_info(self):
+        """The ambiguity set exists for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
+        self._no_cut_sets("cut_sets_info")
 
     def changed_labels(self):
         """Edits by list exist for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
@@ -1381,6 +1454,7 @@ class EmbeddedLatticeGraph(object):
         self._inner._build()
         tr = fg[n:].astype(numpy.float64) * GCGraph.MAX - bg[n:].astype(numpy.float64) * GCGraph.MAX
         self._tail_labels = ~(tr < 0)
+        self._tail_tr = tr
         self._tail_flow = float(numpy.sum(numpy.minimum(fg[n:], bg[n:]).astype(numpy.float64)) * GCGraph.MAX)  # graph.h:423
         self._n = n
 
@@ -1445,6 +1519,22 @@ class EmbeddedLatticeGraph(object):
     def markers(self):
         raise NotImplementedError("medpy_amd: markers is not implemented for a graph whose boundary image has another shape "
                                   "than its markers (EmbeddedLatticeGraph)")
+
+    def source_side(self):
+        """flat, as ``labels()``: the lattice part from the voxel graph; an isolated node is reached from the source iff its
+        t-link points from the source"""
+        return numpy.concatenate([self._inner.source_side().ravel(), self._tail_tr > 0])
+
+    def ambiguous(self):
+        """flat, as ``labels()``: an isolated node is ambiguous iff it holds no t-link at all"""
+        return numpy.concatenate([self._inner.ambiguous().ravel(), self._tail_tr == 0])
+
+    def cut_is_unique(self):
+        return self._inner.cut_is_unique() and not bool(numpy.any(self._tail_tr == 0))
+
+    def cut_sets_info(self):
+        """of the lattice part (mgc_get_cut_sets_info); ``source_cut`` without the isolated nodes' share of the flow"""
+        return self._inner.cut_sets_info()
 
     def stats(self):
         return self._inner.stats()
