@@ -372,6 +372,25 @@ int mgc_labels(mgc_handle h, uint8_t* out);
  * After a mgc_cut_sets that went through, mgc_last_error holds a note of where its time went (device_ms, download_ms). */
 int mgc_cut_sets(mgc_handle h, uint8_t* from_source, uint8_t* ambiguous);
 int mgc_get_cut_sets_info(mgc_handle h, int64_t* out8, double* source_cut);
+
+/* The same three sets at a ROUNDING TOLERANCE.  On floating-point inputs a residual of a few ulp, or of DBL_MIN next to
+ * weights of order 1, is open under one order of the solve's additions and 0.0 under another; mgc_cut_sets_tol judges every residual
+ * against the size of the numbers it came from.  With scale(v) = the largest rcap(u -> w) + rcap(w -> u) over the arc pairs at v (both
+ * ends voxels of the volume), an arc u -> v is open iff rcap > 0 and rcap > tol * max(scale(u), scale(v)); v is a source seed iff its
+ * excess is > tol * max(|t-link as built|, scale(v)), a sink seed iff its residual sink link is.  from_source = what the source seeds
+ * reach along open arcs, to_sink = what reaches a sink seed along them (a backward flood of its own: the labels are not consulted),
+ * ambiguous = neither; 0 / 1 per voxel in C order, any of the three pointers may be NULL.  tol = 0 goes the same way and gives the sets
+ * of mgc_cut_sets and the complement of mgc_labels; 64 * 2^-52 is the granularity the project's parity statement uses.
+ *   States and refusals are those of mgc_cut_sets, checked before anything is written; MGC_ERR_INVALID for tol < 0, tol >= 1 or NaN.  A
+ * call leaves labels, snapshot, residual state, statistics, launch counts and what mgc_get_cut_sets_info reports as they were, and
+ * device_bytes the same.
+ *   mgc_get_cut_sets_tol_info, of the last mgc_cut_sets_tol: out16 = {voxels from_source, to_sink, ambiguous; passes, tile visits, tiles
+ * seeded of the forward flood; the same three of the backward flood; arcs with rcap > 0 that the threshold closed; t-links (excess > 0
+ * or sink link > 0) that it closed; tiles the forward seeding skipped unread; 0, 0, 0, 0}; out4 = {tol, source_cut = capacity of the cut
+ * around from_source, sink_cut = capacity of the cut around the complement of to_sink (flow constant included in both), the largest
+ * scale(v)}.  Either pointer may be NULL.  mgc_last_error holds a note of where the time of the call went. */
+int mgc_cut_sets_tol(mgc_handle h, double tol, uint8_t* from_source, uint8_t* to_sink, uint8_t* ambiguous);
+int mgc_get_cut_sets_tol_info(mgc_handle h, int64_t* out16, double* out4);
 int mgc_what_segment(mgc_handle h, int64_t i, int* segment); /* Graph::what_segment, graph.h:561-571 */
 
 int mgc_get_node_num(mgc_handle h, int64_t* n);

@@ -159,6 +159,8 @@ SIGNATURES = {
     "mgc_labels": (_INT, [_VP, _VP]),
     "mgc_cut_sets": (_INT, [_VP, _VP, _VP]),
     "mgc_get_cut_sets_info": (_INT, [_VP, _VP, C.POINTER(_DBL)]),
+    "mgc_cut_sets_tol": (_INT, [_VP, _DBL, _VP, _VP, _VP]),
+    "mgc_get_cut_sets_tol_info": (_INT, [_VP, _VP, _VP]),
     "mgc_what_segment": (_INT, [_VP, _I64, C.POINTER(_INT)]),
     "mgc_get_node_num": (_INT, [_VP, C.POINTER(_I64)]),
     "mgc_set_param": (_INT, [_VP, C.c_char_p, _I64]),

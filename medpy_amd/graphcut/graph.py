@@ -14,6 +14,9 @@ import numpy
 from .. import _lib
 
 
+ULP64 = 64 * 2.0 ** -52   # the rounding granularity of the project's parity statement, for the ``tol`` of VoxelGraph.source_side & co.
+
+
 class termtype(enum.IntEnum):
     """reference lib/maxflow/src/graph.h:57-61, exposed per class by wrapper.cpp:84-87."""
     SOURCE = 0
@@ -711,25 +714,55 @@ class VoxelGraph(object):
                 cache[want] = plane.view(numpy.bool_).reshape(self._shape)
         return cache[want]
 
-    def source_side(self):
+    CUT_SETS_TOL_INFO_KEYS = ("from_source", "to_sink", "ambiguous", "forward_passes", "forward_visits", "forward_seeded", "backward_passes",
+                              "backward_visits", "backward_seeded", "arcs_closed", "tlinks_closed", "tiles_skipped")
+
+    def _cut_sets_tol(self, tol, want):
+        """one mgc_cut_sets_tol per solve, tolerance and kind of answer: ``want`` = "source_side", "sink_side", "ambiguous" or "info" """
+        tol = float(tol)
+        cache = self.__dict__.setdefault("_cut_sets_cache", {}).setdefault(("tol", tol), {})
+        if want not in cache:
+            plane = None if want == "info" else numpy.empty(self._nodes, dtype=numpy.uint8)
+            self._call("mgc_cut_sets_tol", tol, *[_lib.ptr(plane) if want == w else None for w in ("source_side", "sink_side", "ambiguous")])
+            out, vals = numpy.zeros(16, dtype=numpy.int64), numpy.zeros(4, dtype=numpy.float64)
+            self._call("mgc_get_cut_sets_tol_info", _lib.ptr(out), _lib.ptr(vals))
+            cache["info"] = dict(zip(self.CUT_SETS_TOL_INFO_KEYS, out.tolist()), tol=float(vals[0]), source_cut=float(vals[1]), sink_cut=float(vals[2]),
+                                 scale_max=float(vals[3]))
+            if plane is not None:
+                cache[want] = plane.view(numpy.bool_).reshape(self._shape)
+        return cache[want]
+
+    def source_side(self, tol=None):
         """bool array of the volume's shape, True on the voxels the SOURCE reaches in the residual graph of the maximum flow: the
         source side of the smallest minimum cut (``labels()`` is that of the largest).  After ``maxflow()``; MedpyHipError
-        (ERR_STATE) before it and after an update or edit that has not been solved.  Cached until the next update or edit."""
-        return self._cut_sets("source_side")
+        (ERR_STATE) before it and after an update or edit that has not been solved.  Cached until the next update or edit.
+        ``tol``: None -- an arc is open iff its residual is > 0 (mgc_cut_sets); a number in [0, 1) -- iff it also exceeds ``tol``
+        times the largest arc-pair capacity at either end (mgc_cut_sets_tol, e.g. ``ULP64``): the voxels whose side does not hinge
+        on the rounding of the solve."""
+        return self._cut_sets("source_side") if tol is None else self._cut_sets_tol(tol, "source_side")
 
-    def ambiguous(self):
+    def sink_side(self, tol=None):
+        """bool array, True on the voxels that reach the SINK in the residual graph: ``~labels()`` for ``tol=None`` (no call is made)
+        and, by a backward flood of its own, for ``tol=0.0``; a part of it for a larger ``tol``."""
+        return ~self.labels() if tol is None else self._cut_sets_tol(tol, "sink_side")
+
+    def ambiguous(self, tol=None):
         """bool array, True on the voxels that are neither reachable from the source nor able to reach the sink: some minimum
-        cut has them on the source side, another on the sink side -- where one more stroke would decide something."""
-        return self._cut_sets("ambiguous")
+        cut has them on the source side, another on the sink side -- where one more stroke would decide something.  With a ``tol``
+        also the voxels whose side hinges on a residual below the rounding granularity."""
+        return self._cut_sets("ambiguous") if tol is None else self._cut_sets_tol(tol, "ambiguous")
 
-    def cut_sets_info(self):
+    def cut_sets_info(self, tol=None):
         """dict: voxels ``from_source`` / ``to_sink`` / ``ambiguous``, ``flood_passes``, ``tile_visits``, ``tiles_seeded``,
-        ``tiles_skipped`` of the flood, and ``source_cut``, the capacity of the cut around ``source_side()`` (= ``maxflow()``)"""
-        return dict(self._cut_sets("info"))
+        ``tiles_skipped`` of the flood, and ``source_cut``, the capacity of the cut around ``source_side()`` (= ``maxflow()``).
+        With a ``tol``: the three counts, passes / visits / seeded tiles of the forward and of the backward flood, ``arcs_closed`` and
+        ``tlinks_closed`` by the threshold, ``tiles_skipped``, ``tol``, ``source_cut``, ``sink_cut`` (around ``~sink_side(tol)``) and
+        ``scale_max``, the largest arc-pair capacity."""
+        return dict(self._cut_sets("info") if tol is None else self._cut_sets_tol(tol, "info"))
 
-    def cut_is_unique(self):
+    def cut_is_unique(self, tol=None):
         """is the minimum cut unique, i.e. the ambiguity set empty?  Counted on the device, no volume is read back."""
-        return self._cut_sets("info")["ambiguous"] == 0
+        return (self._cut_sets("info") if tol is None else self._cut_sets_tol(tol, "info"))["ambiguous"] == 0
 
     def what_segment(self, i):
         """Graph::what_segment, reference graph.h:561-571."""
@@ -911,19 +944,23 @@ class SparseGraph(object):
                                   "graph went to the sparse-graph solver, which keeps its residual graph as CSR arcs: the forward "
                                   "flood over tile masks does not apply (labels() is the sink side's complement)" % what)
 
-    def source_side(self):
+    def source_side(self, tol=None):
         """The source side of the smallest minimum cut exists for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
         self._no_cut_sets("source_side")
 
-    def ambiguous(self):
+    def sink_side(self, tol=None):
+        """The thresholded sink side exists for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
+        self._no_cut_sets("sink_side")
+
+    def ambiguous(self, tol=None):
         """The ambiguity set exists for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
         self._no_cut_sets("ambiguous")
 
-    def cut_is_unique(self):
+    def cut_is_unique(self, tol=None):
         """The ambiguity set exists for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
         self._no_cut_sets("cut_is_unique")
 
-    def cut_sets_info(self):
+    def cut_sets_info(self, tol=None):
         """The ambiguity set exists for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
         self._no_cut_sets("cut_sets_info")
 
@@ -1520,21 +1557,26 @@ class EmbeddedLatticeGraph(object):
         raise NotImplementedError("medpy_amd: markers is not implemented for a graph whose boundary image has another shape "
                                   "than its markers (EmbeddedLatticeGraph)")
 
-    def source_side(self):
+    def source_side(self, tol=None):
         """flat, as ``labels()``: the lattice part from the voxel graph; an isolated node is reached from the source iff its
-        t-link points from the source"""
-        return numpy.concatenate([self._inner.source_side().ravel(), self._tail_tr > 0])
+        t-link points from the source (at every ``tol``: its link is the only number at the node)"""
+        return numpy.concatenate([self._inner.source_side(tol).ravel(), self._tail_tr > 0])
 
-    def ambiguous(self):
+    def sink_side(self, tol=None):
+        """flat: an isolated node reaches the sink iff its t-link points to the sink"""
+        return numpy.concatenate([self._inner.sink_side(tol).ravel(), self._tail_tr < 0])
+
+    def ambiguous(self, tol=None):
         """flat, as ``labels()``: an isolated node is ambiguous iff it holds no t-link at all"""
-        return numpy.concatenate([self._inner.ambiguous().ravel(), self._tail_tr == 0])
+        return numpy.concatenate([self._inner.ambiguous(tol).ravel(), self._tail_tr == 0])
 
-    def cut_is_unique(self):
-        return self._inner.cut_is_unique() and not bool(numpy.any(self._tail_tr == 0))
+    def cut_is_unique(self, tol=None):
+        return self._inner.cut_is_unique(tol) and not bool(numpy.any(self._tail_tr == 0))
 
-    def cut_sets_info(self):
-        """of the lattice part (mgc_get_cut_sets_info); ``source_cut`` without the isolated nodes' share of the flow"""
-        return self._inner.cut_sets_info()
+    def cut_sets_info(self, tol=None):
+        """of the lattice part (mgc_get_cut_sets_info / mgc_get_cut_sets_tol_info); the cut capacities without the isolated nodes' share
+        of the flow"""
+        return self._inner.cut_sets_info(tol)
 
     def stats(self):
         return self._inner.stats()
