@@ -5820,129 +5820,6 @@ int mgc_labels(mgc_handle h, uint8_t* out)
     return MGC_OK;
 }
 
-} /* extern "C" */
-
-/* (included here, behind every other kernel of the file: the kernels of the solve keep their places in the code object) */
-#include "mgc_reach_ops.inl"
-
-/* mgc_cut_sets on the kernels of either neighbourhood (mgc_reach_ops.inl).  Everything the flood writes is its own: the mark plane, the
- * stamps, the C-order planes and the count block come from the pool and go back; of the handle it uses the two relabel lists with
- * their counters (empty between two solves, cleared again on the way out), the counter look of the schedule (read_counts), and the
- * scratch of the cut value (d_part, d_part2, one slot of d_scalar).  Labels, label summaries, snapshot and residual state are read only. */
-template <class Dev>
-static int mgc_cut_sets_on(mgc_handle h, const MgcLayout lay, uint8_t* from_source, uint8_t* ambiguous)
-{
-    MgcRange range_("mgc_cut_sets");
-    MgcLattice& L = h->L;
-    const size_t ntv = (size_t)L.ntiles * MGC_TV, nvox8 = ((size_t)h->nvox + 7) & ~(size_t)7;
-    uint8_t *marks = nullptr, *d_fs = nullptr, *d_amb = nullptr;
-    uint32_t* stamp = nullptr;
-    int32_t* cnt3 = nullptr;
-    unsigned long long* info = nullptr;
-    hipError_t e = mgc_dmalloc((void**)&marks, ntv);
-    if (e == hipSuccess) e = mgc_dmalloc((void**)&d_fs, nvox8);
-    if (e == hipSuccess && ambiguous) e = mgc_dmalloc((void**)&d_amb, nvox8);
-    if (e == hipSuccess) e = mgc_dmalloc((void**)&stamp, (size_t)L.ntiles * sizeof(uint32_t));
-    if (e == hipSuccess) e = mgc_dmalloc((void**)&cnt3, (size_t)L.ntiles * 3 * sizeof(int32_t));
-    if (e == hipSuccess) e = mgc_dmalloc((void**)&info, 8 * sizeof(unsigned long long));
-    auto release = [&]() {
-        for (void* p : {(void*)marks, (void*)d_fs, (void*)d_amb, (void*)stamp, (void*)cnt3, (void*)info}) (void)mgc_dfree(p);
-    };
-    unsigned long long h_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    typedef std::chrono::steady_clock Clock;
-    const auto t0 = Clock::now();
-    Dev dev;
-    dev.h = h;
-    const bool timing = h->timing;
-    h->timing = false; /* (the event pairs of a solve's launches are not for these) */
-    const int lists[2] = {lay.rl_base, lay.rl_base + 1};
-    if (e == hipSuccess) e = hipMemsetAsync(marks, 0, ntv, h->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(stamp, 0, (size_t)L.ntiles * sizeof(uint32_t), h->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(info, 0, 8 * sizeof(unsigned long long), h->stream);
-    if (e == hipSuccess) {
-        dev.zero_count(lists[0]);
-        dev.zero_count(lists[1]);
-        dev.flush_zero();
-        /* the label summaries are those of the labels on the handle where the read-out of the solve wrote them (k_labels8: rows of whole
-         * runs of eight); elsewhere the seed filter reads the labels of a tile itself */
-        const uint8_t* tsum = L.dx % 8 == 0 ? (const uint8_t*)h->d_tsum : (const uint8_t*)nullptr;
-        const int wgs = (L.ntiles + 3) / 4;
-        hipLaunchKernelGGL(k_reach_seed, dim3(wgs < 4096 ? wgs : 4096), dim3(256), 0, h->stream, L, tsum, marks, lists[0], lists[0], info);
-        dev.check(hipGetLastError());
-        /* passes in stretches of relabel_batch between two looks at the length of the list the next pass would consume */
-        const int batch = h->params.relabel_batch > 0 ? h->params.relabel_batch : 8;
-        int cnt[MGC_NCOUNT];
-        uint32_t epoch = 0;
-        for (int k = 0;;) {
-            for (int b = 0; b < batch; ++b, ++k) {
-                const int cur = lists[k & 1], nxt = lists[(k + 1) & 1];
-                dev.zero_count(nxt);
-                dev.flush_zero();
-                ++epoch;
-                if (L.ndir == 6) hipLaunchKernelGGL(k_reach_flood<6>, dim3(dev.grid(L.ntiles)), dim3(MGC_TV), 0, h->stream, L, marks, stamp, cur, cur, epoch, nxt, info);
-                else hipLaunchKernelGGL(k_reach_flood<26>, dim3(dev.grid(L.ntiles)), dim3(MGC_TV), 0, h->stream, L, marks, stamp, cur, cur, epoch, nxt, info);
-                dev.check(hipGetLastError());
-            }
-            dev.read_counts(cnt);
-            if (cnt[lists[k & 1]] == 0 || dev.first_error != hipSuccess) break; /* the last pass queued nobody: fixpoint */
-        }
-        dev.zero_count(lists[0]);
-        dev.zero_count(lists[1]);
-        dev.flush_zero();
-        const int wr = (L.ntiles + 3) / 4;
-        hipLaunchKernelGGL(k_reach_readout, dim3(wr < 4096 ? wr : 4096), dim3(256), 0, h->stream, L, (const uint8_t*)marks, d_fs, d_amb, cnt3);
-        hipLaunchKernelGGL(k_reach_sum, dim3(1), dim3(MGC_TV), 0, h->stream, (const int32_t*)cnt3, L.ntiles, info);
-        /* the capacity of the cut (R_s | V \ R_s) by the label-driven kernel of the solve's read-out, on the marks instead of the labels */
-        const int grid = L.ntiles < h->grid_cap * 4 ? L.ntiles : h->grid_cap * 4;
-        hipLaunchKernelGGL(k_cut_value26<0>, dim3((grid + 3) / 4 < 8192 ? (grid + 3) / 4 : 8192), dim3(256), 0, h->stream, L, h->build_args, (const double*)h->d_tr0, (const uint8_t*)d_fs, (const uint8_t*)nullptr, h->d_part);
-        mgc_sum_partials(h, (int64_t)L.ntiles, h->d_scalar + 4);
-        dev.check(hipGetLastError());
-        e = dev.first_error;
-    }
-    h->timing = timing;
-    if (e == hipSuccess) e = hipMemcpyAsync(h->h_scalar, h->d_scalar, 8 * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e == hipSuccess) e = hipMemcpy(h_info, info, sizeof(h_info), hipMemcpyDeviceToHost);
-    const auto t1 = Clock::now();
-    if (e == hipSuccess && from_source) e = mgc_staged_copy(h, d_fs, from_source, (size_t)h->nvox, false);
-    if (e == hipSuccess && ambiguous) e = mgc_staged_copy(h, d_amb, ambiguous, (size_t)h->nvox, false);
-    release();
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return mgc_fail(h, e == hipErrorOutOfMemory ? MGC_ERR_OOM : MGC_ERR_HIP, "mgc_cut_sets: %s", hipGetErrorString(e));
-    }
-    for (int k = 0; k < 8; ++k) h->cut_info[k] = (int64_t)h_info[k];
-    h->cut_info[7] = 0;
-    h->cut_source = h->flow_const + h->h_scalar[4];
-    h->cut_info_valid = true;
-    /* no error: the note says where the time of this call went (tools/gpu_cut_sets.py records it) */
-    (void)mgc_fail(h, MGC_OK, "mgc_cut_sets: device_ms=%.3f download_ms=%.3f", std::chrono::duration<double, std::milli>(t1 - t0).count(),
-                   std::chrono::duration<double, std::milli>(Clock::now() - t1).count());
-    return MGC_OK;
-}
-
-extern "C" {
-
-int mgc_cut_sets(mgc_handle h, uint8_t* from_source, uint8_t* ambiguous)
-{
-    if (!h) return MGC_ERR_INVALID;
-    if (h->nranks > 1) return mgc_fail(h, MGC_ERR_UNSUPPORTED, "mgc_cut_sets: a slab holds a part of the residual graph only (the flood would have to cross the slab borders)");
-    if (!h->built) return mgc_fail(h, MGC_ERR_STATE, "mgc_cut_sets before mgc_build");
-    if (!h->solved) return mgc_fail(h, MGC_ERR_STATE, "mgc_cut_sets before mgc_maxflow (or after an update or edit that the next mgc_maxflow has yet to solve)");
-    if (!h->converged || h->unconverged) return mgc_fail(h, MGC_ERR_STATE, "mgc_cut_sets: the last mgc_maxflow of this handle did not run to a maximum preflow");
-    MGC_HIP(h, hipSetDevice(h->device));
-    return h->L.ndir == 6 ? mgc_cut_sets_on<HipDev>(h, mgc_layout6(), from_source, ambiguous) : mgc_cut_sets_on<HipDev26>(h, mgc_layout26(), from_source, ambiguous);
-}
-
-int mgc_get_cut_sets_info(mgc_handle h, int64_t* out8, double* source_cut)
-{
-    if (!h) return MGC_ERR_INVALID;
-    if (!h->cut_info_valid) return mgc_fail(h, MGC_ERR_STATE, "mgc_get_cut_sets_info before mgc_cut_sets");
-    if (out8) for (int k = 0; k < 8; ++k) out8[k] = h->cut_info[k];
-    if (source_cut) *source_cut = h->cut_source;
-    return MGC_OK;
-}
-
 int mgc_what_segment(mgc_handle h, int64_t i, int* segment)
 {
     if (!h || !segment) return MGC_ERR_INVALID;
@@ -6165,177 +6042,5 @@ int mgc_get_stats(mgc_handle h, mgc_stats* out)
 
 } /* extern "C" */
 
-/* (behind everything else of the file, as mgc_reach_ops.inl before it: the kernels of the solve keep their places in the code object) */
-#include "mgc_reach_tol_ops.inl"
-
-/* mgc_cut_sets_tol on the kernels of either neighbourhood (mgc_reach_tol_ops.inl).  As in mgc_cut_sets_on everything that is written is
- * the call's own and comes from the pool: the scale plane, the thresholded mask plane, two mark planes, the stamps, the C-order planes
- * and the counts; the two relabel lists and their counters carry both floods, one after the other.  The forward flood is k_reach_flood
- * itself, launched on a copy of the lattice whose mask pointer is the thresholded plane.  Labels, label summaries (the forward seeding's
- * skip apart), snapshot and residual state are read only; the backward path reads neither labels nor summaries. */
-template <class Dev>
-static int mgc_cut_sets_tol_on(mgc_handle h, const MgcLayout lay, double tol, uint8_t* from_source, uint8_t* to_sink, uint8_t* ambiguous)
-{
-    MgcRange range_("mgc_cut_sets_tol");
-    MgcLattice& L = h->L;
-    const size_t ntv = (size_t)L.ntiles * MGC_TV, nvox8 = ((size_t)h->nvox + 7) & ~(size_t)7;
-    double* scale = nullptr;
-    void* omask = nullptr;
-    uint8_t *fwd = nullptr, *bwd = nullptr, *d_fs = nullptr, *d_ts = nullptr, *d_amb = nullptr, *d_ns = nullptr;
-    uint32_t* stamp = nullptr;
-    int32_t* cnt3 = nullptr;
-    unsigned long long* info = nullptr;
-    hipError_t e = mgc_dmalloc((void**)&scale, ntv * sizeof(double));
-    if (e == hipSuccess) e = mgc_dmalloc(&omask, ntv * (L.ndir == 6 ? sizeof(uint8_t) : sizeof(uint32_t)));
-    if (e == hipSuccess) e = mgc_dmalloc((void**)&fwd, ntv);
-    if (e == hipSuccess) e = mgc_dmalloc((void**)&bwd, ntv);
-    if (e == hipSuccess) e = mgc_dmalloc((void**)&d_fs, nvox8);
-    if (e == hipSuccess) e = mgc_dmalloc((void**)&d_ns, nvox8);
-    if (e == hipSuccess && to_sink) e = mgc_dmalloc((void**)&d_ts, nvox8);
-    if (e == hipSuccess && ambiguous) e = mgc_dmalloc((void**)&d_amb, nvox8);
-    if (e == hipSuccess) e = mgc_dmalloc((void**)&stamp, (size_t)L.ntiles * sizeof(uint32_t));
-    if (e == hipSuccess) e = mgc_dmalloc((void**)&cnt3, (size_t)L.ntiles * 3 * sizeof(int32_t));
-    if (e == hipSuccess) e = mgc_dmalloc((void**)&info, 16 * sizeof(unsigned long long));
-    auto release = [&]() {
-        for (void* p : {(void*)scale, omask, (void*)fwd, (void*)bwd, (void*)d_fs, (void*)d_ns, (void*)d_ts, (void*)d_amb, (void*)stamp, (void*)cnt3, (void*)info}) (void)mgc_dfree(p);
-    };
-    unsigned long long h_info[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    typedef std::chrono::steady_clock Clock;
-    auto ms_since = [](Clock::time_point a) { return std::chrono::duration<double, std::milli>(Clock::now() - a).count(); };
-    double ms_phase[5] = {0.0, 0.0, 0.0, 0.0, 0.0}; /* scale, open, forward flood, backward flood, read-out (each ends on a drained stream) */
-    const auto t0 = Clock::now();
-    Dev dev;
-    dev.h = h;
-    const bool timing = h->timing;
-    h->timing = false; /* (the event pairs of a solve's launches are not for these) */
-    const int lists[2] = {lay.rl_base, lay.rl_base + 1};
-    if (e == hipSuccess) e = hipMemsetAsync(fwd, 0, ntv, h->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(bwd, 0, ntv, h->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(stamp, 0, (size_t)L.ntiles * sizeof(uint32_t), h->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(info, 0, 16 * sizeof(unsigned long long), h->stream);
-    if (e == hipSuccess) {
-        MgcLattice Lt = L; /* the lattice k_reach_flood sees: the thresholded plane in place of the stored masks */
-        if (L.ndir == 6) Lt.rmask = (uint8_t*)omask;
-        else Lt.rmask32 = (uint32_t*)omask;
-        const int batch = h->params.relabel_batch > 0 ? h->params.relabel_batch : 8;
-        const int wgs = (L.ntiles + 3) / 4 < 4096 ? (L.ntiles + 3) / 4 : 4096;
-        uint32_t epoch = 0;
-        /* passes in stretches of `batch` between two looks at the length of the list the next pass would consume (as mgc_cut_sets_on) */
-        auto flood = [&](bool back) {
-            int cnt[MGC_NCOUNT];
-            for (int k = 0;;) {
-                for (int b = 0; b < batch; ++b, ++k) {
-                    const int cur = lists[k & 1], nxt = lists[(k + 1) & 1];
-                    dev.zero_count(nxt);
-                    dev.flush_zero();
-                    ++epoch;
-                    if (!back) {
-                        if (L.ndir == 6) hipLaunchKernelGGL(k_reach_flood<6>, dim3(dev.grid(L.ntiles)), dim3(MGC_TV), 0, h->stream, Lt, fwd, stamp, cur, cur, epoch, nxt, info);
-                        else hipLaunchKernelGGL(k_reach_flood<26>, dim3(dev.grid(L.ntiles)), dim3(MGC_TV), 0, h->stream, Lt, fwd, stamp, cur, cur, epoch, nxt, info);
-                    } else {
-                        if (L.ndir == 6) hipLaunchKernelGGL(k_reach_flood_back<6>, dim3(dev.grid(L.ntiles)), dim3(MGC_TV), 0, h->stream, L, (const void*)omask, bwd, stamp, cur, cur, epoch, nxt, info + MGC_REACHT_BACK);
-                        else hipLaunchKernelGGL(k_reach_flood_back<26>, dim3(dev.grid(L.ntiles)), dim3(MGC_TV), 0, h->stream, L, (const void*)omask, bwd, stamp, cur, cur, epoch, nxt, info + MGC_REACHT_BACK);
-                    }
-                    dev.check(hipGetLastError());
-                }
-                dev.read_counts(cnt);
-                if (cnt[lists[k & 1]] == 0 || dev.first_error != hipSuccess) break; /* the last pass queued nobody: fixpoint */
-            }
-            dev.zero_count(lists[0]);
-            dev.zero_count(lists[1]);
-            dev.flush_zero();
-        };
-        auto t = Clock::now();
-        if (L.ndir == 6) hipLaunchKernelGGL(k_reach_scale<6>, dim3(dev.grid(L.ntiles)), dim3(MGC_TV), 0, h->stream, L, scale, info);
-        else hipLaunchKernelGGL(k_reach_scale<26>, dim3(dev.grid(L.ntiles)), dim3(MGC_TV), 0, h->stream, L, scale, info);
-        dev.check(hipGetLastError());
-        dev.check(hipStreamSynchronize(h->stream));
-        ms_phase[0] = ms_since(t);
-        t = Clock::now();
-        if (L.ndir == 6) hipLaunchKernelGGL(k_reach_open<6>, dim3(dev.grid(L.ntiles)), dim3(MGC_TV), 0, h->stream, L, (const double*)scale, tol, omask, info);
-        else hipLaunchKernelGGL(k_reach_open<26>, dim3(dev.grid(L.ntiles)), dim3(MGC_TV), 0, h->stream, L, (const double*)scale, tol, omask, info);
-        dev.check(hipGetLastError());
-        dev.check(hipStreamSynchronize(h->stream));
-        ms_phase[1] = ms_since(t);
-        t = Clock::now();
-        dev.zero_count(lists[0]);
-        dev.zero_count(lists[1]);
-        dev.flush_zero();
-        const uint8_t* tsum = L.dx % 8 == 0 ? (const uint8_t*)h->d_tsum : (const uint8_t*)nullptr; /* (as mgc_cut_sets_on; the forward seeding only) */
-        hipLaunchKernelGGL(k_reach_seed_tol<false>, dim3(wgs), dim3(256), 0, h->stream, L, (const uint8_t*)h->d_tflags, (const double*)h->d_tr0, (const double*)scale, tol, tsum, fwd,
-                           lists[0], lists[0], info + MGC_REACH_SEEDED, info + MGC_REACHT_SKIPPED, info + MGC_REACHT_TLINKS_CLOSED);
-        dev.check(hipGetLastError());
-        flood(false);
-        ms_phase[2] = ms_since(t);
-        t = Clock::now();
-        hipLaunchKernelGGL(k_reach_seed_tol<true>, dim3(wgs), dim3(256), 0, h->stream, L, (const uint8_t*)h->d_tflags, (const double*)h->d_tr0, (const double*)scale, tol, (const uint8_t*)nullptr, bwd,
-                           lists[0], lists[0], info + MGC_REACHT_BACK + 2, (unsigned long long*)nullptr, info + MGC_REACHT_TLINKS_CLOSED);
-        dev.check(hipGetLastError());
-        flood(true);
-        ms_phase[3] = ms_since(t);
-        t = Clock::now();
-        hipLaunchKernelGGL(k_reach_readout_tol, dim3(wgs), dim3(256), 0, h->stream, L, (const uint8_t*)fwd, (const uint8_t*)bwd, d_fs, d_ts, d_amb, d_ns, cnt3);
-        hipLaunchKernelGGL(k_reach_sum, dim3(1), dim3(MGC_TV), 0, h->stream, (const int32_t*)cnt3, L.ntiles, info);
-        /* the capacities of the cuts (R_s | V \ R_s) and (V \ R_t | R_t) by the label-driven kernel of the solve's read-out */
-        const int grid = L.ntiles < h->grid_cap * 4 ? L.ntiles : h->grid_cap * 4;
-        const int cwgs = (grid + 3) / 4 < 8192 ? (grid + 3) / 4 : 8192;
-        hipLaunchKernelGGL(k_cut_value26<0>, dim3(cwgs), dim3(256), 0, h->stream, L, h->build_args, (const double*)h->d_tr0, (const uint8_t*)d_fs, (const uint8_t*)nullptr, h->d_part);
-        mgc_sum_partials(h, (int64_t)L.ntiles, h->d_scalar + 4);
-        hipLaunchKernelGGL(k_cut_value26<0>, dim3(cwgs), dim3(256), 0, h->stream, L, h->build_args, (const double*)h->d_tr0, (const uint8_t*)d_ns, (const uint8_t*)nullptr, h->d_part);
-        mgc_sum_partials(h, (int64_t)L.ntiles, h->d_scalar + 5);
-        dev.check(hipGetLastError());
-        e = dev.first_error;
-        if (e == hipSuccess) e = hipMemcpyAsync(h->h_scalar, h->d_scalar, 8 * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        ms_phase[4] = ms_since(t);
-    }
-    h->timing = timing;
-    if (e == hipSuccess) e = hipMemcpy(h_info, info, sizeof(h_info), hipMemcpyDeviceToHost);
-    const auto t1 = Clock::now();
-    if (e == hipSuccess && from_source) e = mgc_staged_copy(h, d_fs, from_source, (size_t)h->nvox, false);
-    if (e == hipSuccess && to_sink) e = mgc_staged_copy(h, d_ts, to_sink, (size_t)h->nvox, false);
-    if (e == hipSuccess && ambiguous) e = mgc_staged_copy(h, d_amb, ambiguous, (size_t)h->nvox, false);
-    release();
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return mgc_fail(h, e == hipErrorOutOfMemory ? MGC_ERR_OOM : MGC_ERR_HIP, "mgc_cut_sets_tol: %s", hipGetErrorString(e));
-    }
-    for (int k = 0; k < 16; ++k) h->cut_tol_info[k] = k < MGC_REACHT_SCALE_MAX ? (int64_t)h_info[k] : 0;
-    double scale_max = 0.0;
-    memcpy(&scale_max, &h_info[MGC_REACHT_SCALE_MAX], sizeof(double));
-    h->cut_tol_vals[0] = tol;
-    h->cut_tol_vals[1] = h->flow_const + h->h_scalar[4];
-    h->cut_tol_vals[2] = h->flow_const + h->h_scalar[5];
-    h->cut_tol_vals[3] = scale_max;
-    h->cut_tol_info_valid = true;
-    /* no error: the note says where the time of this call went (tools/gpu_cut_sets_tol.py records it) */
-    (void)mgc_fail(h, MGC_OK, "mgc_cut_sets_tol: device_ms=%.3f scale_ms=%.3f open_ms=%.3f forward_ms=%.3f backward_ms=%.3f readout_ms=%.3f download_ms=%.3f",
-                   std::chrono::duration<double, std::milli>(t1 - t0).count(), ms_phase[0], ms_phase[1], ms_phase[2], ms_phase[3], ms_phase[4], ms_since(t1));
-    return MGC_OK;
-}
-
-extern "C" {
-
-int mgc_cut_sets_tol(mgc_handle h, double tol, uint8_t* from_source, uint8_t* to_sink, uint8_t* ambiguous)
-{
-    if (!h) return MGC_ERR_INVALID;
-    if (h->nranks > 1) return mgc_fail(h, MGC_ERR_UNSUPPORTED, "mgc_cut_sets_tol: a slab holds a part of the residual graph only (the floods would have to cross the slab borders)");
-    if (!h->built) return mgc_fail(h, MGC_ERR_STATE, "mgc_cut_sets_tol before mgc_build");
-    if (!h->solved) return mgc_fail(h, MGC_ERR_STATE, "mgc_cut_sets_tol before mgc_maxflow (or after an update or edit that the next mgc_maxflow has yet to solve)");
-    if (!h->converged || h->unconverged) return mgc_fail(h, MGC_ERR_STATE, "mgc_cut_sets_tol: the last mgc_maxflow of this handle did not run to a maximum preflow");
-    if (!(tol >= 0.0) || !(tol < 1.0)) return mgc_fail(h, MGC_ERR_INVALID, "mgc_cut_sets_tol: tol must be a number in [0, 1), got %g", tol);
-    MGC_HIP(h, hipSetDevice(h->device));
-    return h->L.ndir == 6 ? mgc_cut_sets_tol_on<HipDev>(h, mgc_layout6(), tol, from_source, to_sink, ambiguous)
-                          : mgc_cut_sets_tol_on<HipDev26>(h, mgc_layout26(), tol, from_source, to_sink, ambiguous);
-}
-
-int mgc_get_cut_sets_tol_info(mgc_handle h, int64_t* out16, double* out4)
-{
-    if (!h) return MGC_ERR_INVALID;
-    if (!h->cut_tol_info_valid) return mgc_fail(h, MGC_ERR_STATE, "mgc_get_cut_sets_tol_info before mgc_cut_sets_tol");
-    if (out16) for (int k = 0; k < 16; ++k) out16[k] = h->cut_tol_info[k];
-    if (out4) for (int k = 0; k < 4; ++k) out4[k] = h->cut_tol_vals[k];
-    return MGC_OK;
-}
-
-} /* extern "C" */
+/* (behind everything else of the file: the kernels of the solve keep their places in the code object) */
+#include "mgc_reach_driver.inl"

@@ -11,13 +11,14 @@
  *   k_reach_seed     one wave per tile: tiles wholly on the sink side are skipped, the others mark their excess > 0 voxels in a
  *                    tile-major byte plane and go on the first work list
  *   k_reach_flood    one workgroup per listed tile: own marks and masks plus the one-voxel halo of the neighbours' marks AND masks
- *                    in LDS, a fixpoint inside the tile, then the neighbour tiles an open arc leads into are queued (stamp de-duplicated)
+ *                    in LDS, a fixpoint inside the tile, then the neighbour tiles an open arc leads into are queued (stamp de-duplicated);
+ *                    <NDIR, BACK>: BACK follows the arcs against their direction (the sink side of mgc_cut_sets_tol, mgc_reach_tol_ops.inl)
  *   k_reach_readout  marks -> C order (from_source) and ambiguous = !mark && height == MGC_HINF, three counts per tile
  *   k_reach_sum      the per-tile counts in a fixed order
  *
- * The step of ONE tile, mgc_reach_tile_step, is plain C++ over (first index, stride, barrier): the kernel runs it with 512 threads
- * and __syncthreads_or, the stand-alone host program of the CPU test tier (tests/hostsim/reach_main.cpp) with one thread and no
- * barrier.  Only mgc_common.h is needed on the host.
+ * The step of ONE tile, mgc_reach_tile_step<NDIR, BACK>, is plain C++ over (first index, stride, barrier): the kernel runs it with 512
+ * threads and __syncthreads_or, the stand-alone host programs of the CPU test tier (tests/hostsim/reach_main.cpp, reach_tol_main.cpp)
+ * with one thread and no barrier.  Only mgc_common.h is needed on the host.
  */
 #ifndef MGC_REACH_OPS_INL
 #define MGC_REACH_OPS_INL
@@ -108,17 +109,55 @@ MGC_HD uint32_t mgc_reach_wake(const uint8_t* mk, const uint32_t* ms, int z, int
     return w;
 }
 
+/* Can cell `me` step along an open arc of ITS OWN into a marked cell?  (Backward: me reaches the sink if somebody it has an open arc
+ * to does.)  A bit towards a cell that is no voxel of the volume finds that cell unmarked. */
+template <int NDIR>
+MGC_HD bool mgc_reach_pull_back(const uint8_t* mk, const uint32_t* ms, int me)
+{
+    const uint32_t m = ms[me];
+    for (int d = 0; d < NDIR; ++d) {
+        if (!((m >> d) & 1u)) continue;
+        int dz, dy, dx;
+        mgc_reach_offset<NDIR>(d, dz, dy, dx);
+        if (mk[me + (dz * 10 + dy) * 10 + dx]) return true;
+    }
+    return false;
+}
+
+/* The neighbour tiles that hold an unmarked voxel with an open arc INTO the marked voxel (z, y, x) of this tile, judged by the
+ * neighbour voxel's staged mask: the wake bits of mgc_reach_wake. */
+template <int NDIR>
+MGC_HD uint32_t mgc_reach_wake_back(const uint8_t* mk, const uint32_t* ms, int z, int y, int x)
+{
+    uint32_t w = 0;
+    for (int d = 0; d < NDIR; ++d) {
+        int dz, dy, dx;
+        mgc_reach_offset<NDIR>(d, dz, dy, dx);
+        const int nz = z + dz, ny = y + dy, nx = x + dx;
+        const int oz = nz < 0 ? -1 : (nz > 7 ? 1 : 0), oy = ny < 0 ? -1 : (ny > 7 ? 1 : 0), ox = nx < 0 ? -1 : (nx > 7 ? 1 : 0);
+        if (!(oz | oy | ox)) continue;
+        const int n = mgc_reach_cell(nz, ny, nx);
+        if ((ms[n] & MGC_REACH_VALID) && !mk[n] && ((ms[n] >> mgc_reach_opposite<NDIR>(d)) & 1u)) w |= 1u << ((oz + 1) * 9 + (oy + 1) * 3 + (ox + 1));
+    }
+    return w;
+}
+
 /* The flood step of ONE tile, run by `nt` workers of which this is number t0; sync(v) is a barrier that returns the OR of every
  * worker's v (one worker: the identity).  mk / ms: MGC_REACH_BLOCK cells shared by the workers.  marks: the tile-major mark plane,
- * masks: L.rmask (6 directions) or L.rmask32 (26).  Returns the worker's share of the wake bits (mgc_reach_wake), to be OR-ed.
+ * masks: a tile-major mask plane in the bit layout of L.rmask (6 directions) or L.rmask32 (26).  Returns the worker's share of the
+ * wake bits (mgc_reach_wake / mgc_reach_wake_back), to be OR-ed.
+ *   BACK = false, the default, follows the arcs the way they point: `me` gets a mark when a marked neighbour n exists and the arc n -> me is open,
+ *   the NEIGHBOUR's bit towards me.  BACK = true follows them against their direction: `me` gets a mark when a marked neighbour n
+ *   exists and the arc me -> n is open, MY OWN bit towards the neighbour.  Staging, fixpoint and write-back are the same.
  *   Marks only ever go 0 -> 1.  A worker may therefore read a cell another one is marking in the same sweep, and a tile may read a
  *   halo mark its neighbour is writing in the same launch: a stale 0 costs one more sweep or one more visit -- whoever marks a
- *   border voxel with an open arc into an unmarked neighbour voxel queues that neighbour for the NEXT launch, which sees the mark --
- *   never a wrong set.  The same reasoning as for the labels of a relabel pass, which only ever go down.
+ *   border voxel with an open arc (in the flood's direction) between it and an unmarked neighbour voxel queues that neighbour for the
+ *   NEXT launch, which sees the mark -- never a wrong set.  The same reasoning as for the labels of a relabel pass, which only ever
+ *   go down.
  *   The wake test runs over every marked voxel of the tile, not only the ones this visit marked: the seed voxels of the first
- *   pass were marked by k_reach_seed.  A queued neighbour marks at least the voxel it was queued for (it is a voxel of the volume
- *   and the arc is open) unless somebody did so meanwhile, so the lists run empty. */
-template <int NDIR, class Mask, class Sync>
+ *   pass were marked by the seeding kernel.  A queued neighbour marks at least the voxel it was queued for (it is a voxel of the
+ *   volume and the arc is open) unless somebody did so meanwhile, so the lists run empty. */
+template <int NDIR, bool BACK = false, class Mask, class Sync>
 MGC_HD uint32_t mgc_reach_tile_step(const MgcLattice& L, uint8_t* marks, const Mask* masks, int tile, uint8_t* mk, uint32_t* ms, int t0, int nt, Sync& sync)
 {
     int tz, ty, tx;
@@ -141,7 +180,7 @@ MGC_HD uint32_t mgc_reach_tile_step(const MgcLattice& L, uint8_t* marks, const M
         int changed = 0;
         for (int v = t0; v < MGC_TV; v += nt) {
             const int me = mgc_reach_cell(v >> 6, (v >> 3) & 7, v & 7);
-            if (!mk[me] && (ms[me] & MGC_REACH_VALID) && mgc_reach_pull<NDIR>(mk, ms, me)) {
+            if (!mk[me] && (ms[me] & MGC_REACH_VALID) && (BACK ? mgc_reach_pull_back<NDIR>(mk, ms, me) : mgc_reach_pull<NDIR>(mk, ms, me))) {
                 mk[me] = 1;
                 changed = 1;
             }
@@ -154,7 +193,7 @@ MGC_HD uint32_t mgc_reach_tile_step(const MgcLattice& L, uint8_t* marks, const M
         if (!mk[mgc_reach_cell(z, y, x)]) continue;
         const int64_t at = (int64_t)tile * MGC_TV + v;
         if (!marks[at]) marks[at] = 1;
-        wake |= mgc_reach_wake<NDIR>(mk, ms, z, y, x);
+        wake |= BACK ? mgc_reach_wake_back<NDIR>(mk, ms, z, y, x) : mgc_reach_wake<NDIR>(mk, ms, z, y, x);
     }
     return wake;
 }
@@ -175,6 +214,24 @@ struct MgcReachBarrier {
     __device__ __forceinline__ int operator()(int v) const { return __syncthreads_or(v); }
 };
 
+/* The row of the one-wave-per-tile kernels: lane = row (z, y) of eight voxels of `tile`, x0 its first x.  Returns the number of the
+ * row's voxels that lie inside the volume (0 for a padding row). */
+__device__ __forceinline__ int mgc_reach_row(const MgcLattice& L, int tile, int lane, int64_t& z, int64_t& y, int64_t& x0)
+{
+    int tz, ty, tx;
+    mgc_tile_coords(L, tile, tz, ty, tx);
+    z = (int64_t)tz * 8 + (lane >> 3), y = (int64_t)ty * 8 + (lane & 7), x0 = (int64_t)tx * 8;
+    return !(z < L.dz && y < L.dy) ? 0 : (L.dx - x0 < 8 ? (int)(L.dx - x0) : 8);
+}
+
+/* `tile` on list `list`, counted in counter slot `cnt`, in the shard of this workgroup */
+__device__ __forceinline__ void mgc_reach_append(const MgcLattice& L, int list, int cnt, int tile)
+{
+    const int sh = (int)(blockIdx.x & (unsigned)(L.nshard - 1));
+    const int pos = atomicAdd(mgc_counter(L, cnt, sh), 1);
+    L.list[list][(int64_t)sh * L.shard_cap + pos] = tile;
+}
+
 /* One wave per tile, lane = row (z, y) of eight voxels.  tsum: the label summaries k_labels8 left (0: every voxel of the tile can
  * reach the sink -- no voxel of R_s lives there, the tile is skipped unread) or NULL where the read-out keeps none (rows that are
  * no whole runs of eight): the wave then looks at the tile's labels itself.  Padding voxels of partial tiles are never marked.
@@ -184,10 +241,8 @@ __global__ __launch_bounds__(256) void k_reach_seed(MgcLattice L, const uint8_t*
     const int lane = threadIdx.x & 63;
     unsigned long long seeded = 0, skipped = 0; /* (lane 0 of each wave) */
     for (int tile = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6); tile < L.ntiles; tile += (int)gridDim.x * 4) {
-        int tz, ty, tx;
-        mgc_tile_coords(L, tile, tz, ty, tx);
-        const int64_t z = (int64_t)tz * 8 + (lane >> 3), y = (int64_t)ty * 8 + (lane & 7), x0 = (int64_t)tx * 8;
-        const int nx = !(z < L.dz && y < L.dy) ? 0 : (L.dx - x0 < 8 ? (int)(L.dx - x0) : 8); /* voxels of this row inside the volume */
+        int64_t z, y, x0;
+        const int nx = mgc_reach_row(L, tile, lane, z, y, x0);
         bool skip;
         if (tsum) skip = tsum[tile] == 0;
         else {
@@ -210,11 +265,7 @@ __global__ __launch_bounds__(256) void k_reach_seed(MgcLattice L, const uint8_t*
             if (k < nx && ep[k] > 0.0) m |= 1ull << (8 * k);
         if (m) *(unsigned long long*)(marks + (int64_t)tile * MGC_TV + lane * 8) = m;
         if (__ballot(m != 0ull) != 0ull) {
-            if (lane == 0) {
-                const int sh = (int)(blockIdx.x & (unsigned)(L.nshard - 1));
-                const int pos = atomicAdd(mgc_counter(L, cnt, sh), 1);
-                L.list[list][(int64_t)sh * L.shard_cap + pos] = tile;
-            }
+            if (lane == 0) mgc_reach_append(L, list, cnt, tile);
             seeded++;
         }
     }
@@ -224,10 +275,12 @@ __global__ __launch_bounds__(256) void k_reach_seed(MgcLattice L, const uint8_t*
     }
 }
 
-/* One workgroup per tile of list `list` (length in counter slot `cnt`): mgc_reach_tile_step, then every neighbour tile an open arc
- * leads into goes on list `next` unless this pass (stamp == epoch) has queued it already.  A pass over an empty list does nothing. */
-template <int NDIR>
-__global__ __launch_bounds__(MGC_TV) void k_reach_flood(MgcLattice L, uint8_t* marks, uint32_t* stamp, int list, int cnt, uint32_t epoch, int next, unsigned long long* info)
+/* One workgroup per tile of list `list` (length in counter slot `cnt`): mgc_reach_tile_step<NDIR, BACK> on the mask plane `masks`
+ * (uint8_t for 6 directions, uint32_t for 26: the stored L.rmask / L.rmask32 or a thresholded plane), then every neighbour tile the
+ * step's wake bits name goes on list `next` unless this pass (stamp == epoch) has queued it already.  info: passes at [0], visits at
+ * [1].  A pass over an empty list does nothing. */
+template <int NDIR, bool BACK>
+__global__ __launch_bounds__(MGC_TV) void k_reach_flood(MgcLattice L, const void* masks, uint8_t* marks, uint32_t* stamp, int list, int cnt, uint32_t epoch, int next, unsigned long long* info)
 {
     __shared__ uint8_t mk[MGC_REACH_BLOCK];
     __shared__ uint32_t ms[MGC_REACH_BLOCK];
@@ -236,26 +289,22 @@ __global__ __launch_bounds__(MGC_TV) void k_reach_flood(MgcLattice L, uint8_t* m
     MgcListView view;
     const int n = mgc_list_view(L, cnt, view);
     if (blockIdx.x == 0 && t == 0 && n > 0) {
-        atomicAdd(info + MGC_REACH_PASSES, 1ull);
-        atomicAdd(info + MGC_REACH_VISITS, (unsigned long long)n);
+        atomicAdd(info + 0, 1ull);
+        atomicAdd(info + 1, (unsigned long long)n);
     }
     MgcReachBarrier barrier;
     for (int i = blockIdx.x; i < n; i += gridDim.x) {
         const int tile = mgc_list_at(L, list, view, i);
         if (t == 0) wake_all = 0u;
         uint32_t wake;
-        if (NDIR == 6) wake = mgc_reach_tile_step<6>(L, marks, (const uint8_t*)L.rmask, tile, mk, ms, t, MGC_TV, barrier);
-        else wake = mgc_reach_tile_step<26>(L, marks, (const uint32_t*)L.rmask32, tile, mk, ms, t, MGC_TV, barrier);
+        if (NDIR == 6) wake = mgc_reach_tile_step<6, BACK>(L, marks, (const uint8_t*)masks, tile, mk, ms, t, MGC_TV, barrier);
+        else wake = mgc_reach_tile_step<26, BACK>(L, marks, (const uint32_t*)masks, tile, mk, ms, t, MGC_TV, barrier);
         if (wake) atomicOr(&wake_all, wake);
         __syncthreads();
         const uint32_t w = wake_all;
         if (t < 27 && ((w >> t) & 1u)) {
             const int nt = mgc_reach_wake_tile(L, tile, t);
-            if (nt >= 0 && atomicExch(stamp + nt, epoch) != epoch) {
-                const int sh = (int)(blockIdx.x & (unsigned)(L.nshard - 1));
-                const int pos = atomicAdd(mgc_counter(L, next, sh), 1);
-                L.list[next][(int64_t)sh * L.shard_cap + pos] = nt;
-            }
+            if (nt >= 0 && atomicExch(stamp + nt, epoch) != epoch) mgc_reach_append(L, next, next, nt);
         }
         __syncthreads(); /* (the next tile of this workgroup rewrites the block and the wake word) */
     }
@@ -268,10 +317,8 @@ __global__ __launch_bounds__(256) void k_reach_readout(MgcLattice L, const uint8
     const int lane = threadIdx.x & 63;
     const bool rows8 = L.dx % 8 == 0;
     for (int tile = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6); tile < L.ntiles; tile += (int)gridDim.x * 4) {
-        int tz, ty, tx;
-        mgc_tile_coords(L, tile, tz, ty, tx);
-        const int64_t z = (int64_t)tz * 8 + (lane >> 3), y = (int64_t)ty * 8 + (lane & 7), x0 = (int64_t)tx * 8;
-        const int nx = !(z < L.dz && y < L.dy) ? 0 : (L.dx - x0 < 8 ? (int)(L.dx - x0) : 8);
+        int64_t z, y, x0;
+        const int nx = mgc_reach_row(L, tile, lane, z, y, x0);
         const unsigned long long m = *(const unsigned long long*)(marks + (int64_t)tile * MGC_TV + lane * 8);
         const int4* hp = (const int4*)(L.height + (int64_t)tile * MGC_TV + lane * 8);
         const int4 a = hp[0], b = hp[1];

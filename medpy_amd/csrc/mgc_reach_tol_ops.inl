@@ -11,13 +11,12 @@
  *                       the bit layout of rmask / rmask32 (bits towards the outside of the volume and padding voxels: 0); counts the
  *                       arcs with rcap > 0 that the threshold closed
  *   k_reach_seed_tol    one wave per tile: marks the source seeds (or the sink seeds) and lists their tiles
- *   (forward flood)     k_reach_flood of mgc_reach_ops.inl as it is, on a lattice whose mask pointer is the thresholded plane
- *   k_reach_flood_back  one workgroup per listed tile: mgc_reach_tile_step_back, the mirror image of the forward step
+ *   (both floods)       k_reach_flood<NDIR, false | true> of mgc_reach_ops.inl, on the thresholded plane
  *   k_reach_readout_tol the two mark planes -> C order: from_source, to_sink, ambiguous, and the plane "not to_sink" the cut value
  *                       kernel reads; three counts per tile for k_reach_sum
  *
- * The steps of ONE tile are plain C++ over (first index, stride[, barrier]) as in mgc_reach_ops.inl: the kernels run them with 512
- * threads, tests/hostsim/reach_tol_main.cpp with one.
+ * The scale and open steps of ONE tile are plain C++ over (first index, stride) as the flood step of mgc_reach_ops.inl: the kernels
+ * run them with 512 threads, tests/hostsim/reach_tol_main.cpp with one.
  */
 #ifndef MGC_REACH_TOL_OPS_INL
 #define MGC_REACH_TOL_OPS_INL
@@ -26,7 +25,7 @@
 #include "mgc_reach_tol.h"
 
 /* slots of the info block (mgc_get_cut_sets_tol_info): 0 .. 2 the counts as in mgc_reach_ops.inl, 3 .. 5 passes / visits / seeded tiles
- * of the forward flood (the slots k_reach_flood writes), then: */
+ * of the forward flood, then: */
 #define MGC_REACHT_BACK 6          /* .. 8: passes, visits, seeded tiles of the backward flood */
 #define MGC_REACHT_ARCS_CLOSED 9   /* arcs with rcap > 0 that are not open at tol */
 #define MGC_REACHT_TLINKS_CLOSED 10 /* voxels with excess > 0, plus voxels with sink > 0, that are no seeds at tol */
@@ -108,83 +107,6 @@ MGC_HD int mgc_reach_open_tile(const MgcLattice& L, const double* rcap, const do
     return closed;
 }
 
-/* Can cell `me` step along an open arc of ITS OWN into a marked cell?  (Backward: me reaches the sink if somebody it has an open arc
- * to does.)  A bit towards a cell that is no voxel of the volume finds that cell unmarked. */
-template <int NDIR>
-MGC_HD bool mgc_reach_pull_back(const uint8_t* mk, const uint32_t* ms, int me)
-{
-    const uint32_t m = ms[me];
-    for (int d = 0; d < NDIR; ++d) {
-        if (!((m >> d) & 1u)) continue;
-        int dz, dy, dx;
-        mgc_reach_offset<NDIR>(d, dz, dy, dx);
-        if (mk[me + (dz * 10 + dy) * 10 + dx]) return true;
-    }
-    return false;
-}
-
-/* The neighbour tiles that hold an unmarked voxel with an open arc INTO the marked voxel (z, y, x) of this tile, judged by the
- * neighbour voxel's staged mask: the wake bits of mgc_reach_wake. */
-template <int NDIR>
-MGC_HD uint32_t mgc_reach_wake_back(const uint8_t* mk, const uint32_t* ms, int z, int y, int x)
-{
-    uint32_t w = 0;
-    for (int d = 0; d < NDIR; ++d) {
-        int dz, dy, dx;
-        mgc_reach_offset<NDIR>(d, dz, dy, dx);
-        const int nz = z + dz, ny = y + dy, nx = x + dx;
-        const int oz = nz < 0 ? -1 : (nz > 7 ? 1 : 0), oy = ny < 0 ? -1 : (ny > 7 ? 1 : 0), ox = nx < 0 ? -1 : (nx > 7 ? 1 : 0);
-        if (!(oz | oy | ox)) continue;
-        const int n = mgc_reach_cell(nz, ny, nx);
-        if ((ms[n] & MGC_REACH_VALID) && !mk[n] && ((ms[n] >> mgc_reach_opposite<NDIR>(d)) & 1u)) w |= 1u << ((oz + 1) * 9 + (oy + 1) * 3 + (ox + 1));
-    }
-    return w;
-}
-
-/* The backward flood step of ONE tile: mgc_reach_tile_step with the arcs turned round.  `me` gets a mark when a marked neighbour n
- * exists and the arc me -> n is open: me's own bit.  Staging, fixpoint, the 0 -> 1 argument for races and the reason why the wake test
- * runs over every marked voxel are those of the forward step; a queued neighbour tile marks at least the voxel it was queued for. */
-template <int NDIR, class Mask, class Sync>
-MGC_HD uint32_t mgc_reach_tile_step_back(const MgcLattice& L, uint8_t* marks, const Mask* masks, int tile, uint8_t* mk, uint32_t* ms, int t0, int nt, Sync& sync)
-{
-    int tz, ty, tx;
-    mgc_tile_coords(L, tile, tz, ty, tx);
-    for (int k = t0; k < MGC_REACH_BLOCK; k += nt) {
-        int loc;
-        const int home = mgc_reach_cell_home<NDIR>(L, tz, ty, tx, k, loc);
-        uint8_t m = 0;
-        uint32_t a = 0;
-        if (home >= 0) {
-            const int64_t at = (int64_t)home * MGC_TV + loc;
-            m = marks[at];
-            a = (uint32_t)masks[at] | MGC_REACH_VALID;
-        }
-        mk[k] = m;
-        ms[k] = a;
-    }
-    sync(0);
-    for (;;) {
-        int changed = 0;
-        for (int v = t0; v < MGC_TV; v += nt) {
-            const int me = mgc_reach_cell(v >> 6, (v >> 3) & 7, v & 7);
-            if (!mk[me] && (ms[me] & MGC_REACH_VALID) && mgc_reach_pull_back<NDIR>(mk, ms, me)) {
-                mk[me] = 1;
-                changed = 1;
-            }
-        }
-        if (!sync(changed)) break;
-    }
-    uint32_t wake = 0;
-    for (int v = t0; v < MGC_TV; v += nt) {
-        const int z = v >> 6, y = (v >> 3) & 7, x = v & 7;
-        if (!mk[mgc_reach_cell(z, y, x)]) continue;
-        const int64_t at = (int64_t)tile * MGC_TV + v;
-        if (!marks[at]) marks[at] = 1;
-        wake |= mgc_reach_wake_back<NDIR>(mk, ms, z, y, x);
-    }
-    return wake;
-}
-
 #if defined(__HIPCC__)
 
 template <int NDIR>
@@ -230,10 +152,8 @@ __global__ __launch_bounds__(256) void k_reach_seed_tol(MgcLattice L, const uint
     unsigned long long seeded = 0, skipped = 0;
     int closed = 0;
     for (int tile = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6); tile < L.ntiles; tile += (int)gridDim.x * 4) {
-        int tz, ty, tx;
-        mgc_tile_coords(L, tile, tz, ty, tx);
-        const int64_t z = (int64_t)tz * 8 + (lane >> 3), y = (int64_t)ty * 8 + (lane & 7), x0 = (int64_t)tx * 8;
-        const int nx = !(z < L.dz && y < L.dy) ? 0 : (L.dx - x0 < 8 ? (int)(L.dx - x0) : 8); /* voxels of this row inside the volume */
+        int64_t z, y, x0;
+        const int nx = mgc_reach_row(L, tile, lane, z, y, x0);
         if (!BACK && tsum && tsum[tile] == 0) { /* (wave-uniform) */
             skipped++;
             continue;
@@ -253,11 +173,7 @@ __global__ __launch_bounds__(256) void k_reach_seed_tol(MgcLattice L, const uint
         }
         if (m) *(unsigned long long*)(marks + at) = m;
         if (__ballot(m != 0ull) != 0ull) {
-            if (lane == 0) {
-                const int sh = (int)(blockIdx.x & (unsigned)(L.nshard - 1));
-                const int pos = atomicAdd(mgc_counter(L, cnt, sh), 1);
-                L.list[list][(int64_t)sh * L.shard_cap + pos] = tile;
-            }
+            if (lane == 0) mgc_reach_append(L, list, cnt, tile);
             seeded++;
         }
     }
@@ -270,43 +186,6 @@ __global__ __launch_bounds__(256) void k_reach_seed_tol(MgcLattice L, const uint
     }
 }
 
-/* k_reach_flood with the arcs turned round, on the mask plane it is given: one workgroup per tile of list `list`, then every neighbour
- * tile that holds an unmarked voxel with an open arc into a marked border voxel goes on list `next`.  info: passes at [0], visits at [1]. */
-template <int NDIR>
-__global__ __launch_bounds__(MGC_TV) void k_reach_flood_back(MgcLattice L, const void* omask, uint8_t* marks, uint32_t* stamp, int list, int cnt, uint32_t epoch, int next, unsigned long long* info)
-{
-    __shared__ uint8_t mk[MGC_REACH_BLOCK];
-    __shared__ uint32_t ms[MGC_REACH_BLOCK];
-    __shared__ uint32_t wake_all;
-    const int t = threadIdx.x;
-    MgcListView view;
-    const int n = mgc_list_view(L, cnt, view);
-    if (blockIdx.x == 0 && t == 0 && n > 0) {
-        atomicAdd(info + 0, 1ull);
-        atomicAdd(info + 1, (unsigned long long)n);
-    }
-    MgcReachBarrier barrier;
-    for (int i = blockIdx.x; i < n; i += gridDim.x) {
-        const int tile = mgc_list_at(L, list, view, i);
-        if (t == 0) wake_all = 0u;
-        uint32_t wake;
-        if (NDIR == 6) wake = mgc_reach_tile_step_back<6>(L, marks, (const uint8_t*)omask, tile, mk, ms, t, MGC_TV, barrier);
-        else wake = mgc_reach_tile_step_back<26>(L, marks, (const uint32_t*)omask, tile, mk, ms, t, MGC_TV, barrier);
-        if (wake) atomicOr(&wake_all, wake);
-        __syncthreads();
-        const uint32_t w = wake_all;
-        if (t < 27 && ((w >> t) & 1u)) {
-            const int nt = mgc_reach_wake_tile(L, tile, t);
-            if (nt >= 0 && atomicExch(stamp + nt, epoch) != epoch) {
-                const int sh = (int)(blockIdx.x & (unsigned)(L.nshard - 1));
-                const int pos = atomicAdd(mgc_counter(L, next, sh), 1);
-                L.list[next][(int64_t)sh * L.shard_cap + pos] = nt;
-            }
-        }
-        __syncthreads(); /* (the next tile of this workgroup rewrites the block and the wake word) */
-    }
-}
-
 /* One wave per tile, lane = row (z, y): the two mark planes to C order.  from_source = forward mark, to_sink = backward mark,
  * ambiguous = neither, not_sink = !to_sink (the "source side" plane of the cut around V \ R_t); each output may be NULL.
  * cnt3[3 * tile + {0, 1, 2}] = voxels of the tile from the source / to the sink / ambiguous. */
@@ -316,10 +195,8 @@ __global__ __launch_bounds__(256) void k_reach_readout_tol(MgcLattice L, const u
     const int lane = threadIdx.x & 63;
     const bool rows8 = L.dx % 8 == 0;
     for (int tile = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6); tile < L.ntiles; tile += (int)gridDim.x * 4) {
-        int tz, ty, tx;
-        mgc_tile_coords(L, tile, tz, ty, tx);
-        const int64_t z = (int64_t)tz * 8 + (lane >> 3), y = (int64_t)ty * 8 + (lane & 7), x0 = (int64_t)tx * 8;
-        const int nx = !(z < L.dz && y < L.dy) ? 0 : (L.dx - x0 < 8 ? (int)(L.dx - x0) : 8);
+        int64_t z, y, x0;
+        const int nx = mgc_reach_row(L, tile, lane, z, y, x0);
         const unsigned long long ones = 0x0101010101010101ull;
         const unsigned long long inside = nx >= 8 ? ones : (ones & ((1ull << (8 * nx)) - 1ull));
         unsigned long long f = *(const unsigned long long*)(fwd + (int64_t)tile * MGC_TV + lane * 8);

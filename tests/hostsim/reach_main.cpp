@@ -9,35 +9,16 @@
  * The masks are as hostile as the tile-major planes allow: directed (bit d of u says nothing about the way back), random bits on
  * the padding voxels of partial tiles and on directions that leave the volume.  Neither may ever carry a mark.
  *
+ * The same body runs the backward flood of mgc_cut_sets_tol (BACK): on every case the backward flood must mark what the forward flood
+ * marks on the transposed masks.
+ *
  * Built and run by tests/test_cut_sets_host.py, plainly and with -fsanitize=address,undefined.  Prints what failed; exit code 0 = all passed.
  */
-#include <algorithm>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <queue>
-#include <random>
-#include <vector>
 
 #include "../../medpy_amd/csrc/mgc_reach_ops.inl"
-
-struct NoBarrier {
-    int operator()(int v) const { return v; }
-};
-
-static MgcLattice lattice(int64_t dz, int64_t dy, int64_t dx, int ndir)
-{
-    MgcLattice L;
-    memset(&L, 0, sizeof(L));
-    L.dz = dz; L.dy = dy; L.dx = dx;
-    L.nvox = dz * dy * dx;
-    L.gz = (int)((dz + 7) / 8); L.gy = (int)((dy + 7) / 8); L.gx = (int)((dx + 7) / 8);
-    L.ntiles = L.gz * L.gy * L.gx;
-    L.tz_own_hi = L.gz;
-    L.ndir = ndir;
-    L.nshard = 1;
-    return L;
-}
+#include "reach_host.h"
 
 struct Result {
     int passes = 0;
@@ -96,33 +77,8 @@ static int run_case(int64_t dz, int64_t dy, int64_t dx, double p_open, double p_
         }
     }
     /* the flood, tile by tile */
-    std::vector<int> cur, nxt;
-    std::vector<uint32_t> stamp(L.ntiles, 0);
-    for (int tile = 0; tile < L.ntiles; ++tile)
-        for (int v = 0; v < MGC_TV; ++v)
-            if (marks[(size_t)tile * MGC_TV + v]) { cur.push_back(tile); break; }
-    std::vector<uint8_t> mk(MGC_REACH_BLOCK);
-    std::vector<uint32_t> ms(MGC_REACH_BLOCK);
-    NoBarrier sync;
-    uint32_t epoch = 0;
-    while (!cur.empty()) {
-        ++epoch;
-        res.passes++;
-        res.visits += (long)cur.size();
-        if (res.passes > 100000) { printf("the flood does not end\n"); return 1; }
-        std::shuffle(cur.begin(), cur.end(), rng);
-        for (int tile : cur) {
-            const uint32_t wake = mgc_reach_tile_step<NDIR>(L, marks.data(), masks.data(), tile, mk.data(), ms.data(), 0, 1, sync);
-            for (int c = 0; c < 27; ++c) {
-                if (!((wake >> c) & 1u)) continue;
-                const int nt = mgc_reach_wake_tile(L, tile, c);
-                if (nt < 0) { printf("tile %d wakes a tile outside the grid (bit %d)\n", tile, c); return 1; }
-                if (stamp[nt] != epoch) { stamp[nt] = epoch; nxt.push_back(nt); }
-            }
-        }
-        cur.swap(nxt);
-        nxt.clear();
-    }
+    const std::vector<uint8_t> seeds = marks;
+    if (flood<NDIR, Mask>(L, marks, masks, false, rng, res.passes, res.visits)) return 1;
     long bad = 0, padding = 0, count = 0;
     for (size_t i = 0; i < ntv; ++i)
         if (marks[i] && !inside[i]) padding++;
@@ -136,6 +92,34 @@ static int run_case(int64_t dz, int64_t dy, int64_t dx, double p_open, double p_
     if (bad || padding) {
         printf("%d directions, %lld x %lld x %lld, p %.2f, seed %u: %ld voxels differ from the BFS, %ld padding voxels marked (BFS marks %ld)\n",
                NDIR, (long long)dz, (long long)dy, (long long)dx, p_open, seed, bad, padding, count);
+        return 1;
+    }
+    /* One body serves both directions: the backward flood from the seeds on these masks marks exactly what the forward flood from the
+     * same seeds marks on the TRANSPOSED masks -- bit d of v = bit opposite(d) of v + offset(d), 0 where that voxel lies outside the
+     * volume; padding voxels keep their random bits. */
+    std::vector<Mask> transposed = masks;
+    for (int64_t id = 0; id < L.nvox; ++id) {
+        uint32_t m = 0;
+        for (int d = 0; d < NDIR; ++d) {
+            const int64_t n = neighbour<NDIR>(L, id, d);
+            if (n < 0) continue;
+            int tile, loc;
+            mgc_node_to_tile(L, n, tile, loc);
+            m |= (((uint32_t)masks[(size_t)tile * MGC_TV + loc] >> mgc_reach_opposite<NDIR>(d)) & 1u) << d;
+        }
+        int tile, loc;
+        mgc_node_to_tile(L, id, tile, loc);
+        transposed[(size_t)tile * MGC_TV + loc] = (Mask)m;
+    }
+    std::vector<uint8_t> back = seeds, fwd_t = seeds;
+    int passes = 0;
+    long visits = 0;
+    if (flood<NDIR, Mask>(L, back, masks, true, rng, passes, visits) || flood<NDIR, Mask>(L, fwd_t, transposed, false, rng, passes, visits)) return 1;
+    if (back != fwd_t) {
+        long differ = 0;
+        for (size_t i = 0; i < ntv; ++i) differ += back[i] != fwd_t[i];
+        printf("%d directions, %lld x %lld x %lld, p %.2f, seed %u: the backward flood and the forward flood on the transposed masks differ in %ld cells\n",
+               NDIR, (long long)dz, (long long)dy, (long long)dx, p_open, seed, differ);
         return 1;
     }
     return 0;

@@ -1,94 +1,28 @@
 /*
- * reach_tol_main.cpp -- stand-alone host program of the CPU test tier for mgc_cut_sets_tol: the scale step, the open step
- * and the backward tile step of medpy_amd/csrc/mgc_reach_tol_ops.inl, compiled for the host and run with one thread, against a plain
+ * reach_tol_main.cpp -- stand-alone host program of the CPU test tier for mgc_cut_sets_tol: the scale step and the open
+ * step of medpy_amd/csrc/mgc_reach_tol_ops.inl and both directions of the tile step of mgc_reach_ops.inl, compiled for the host and run with one thread, against a plain
  * per-voxel restatement of the rule over the C-order volume and a voxel BFS.
  *
  * The residual planes are as hostile as the tile-major layout allows: directed (rcap of u -> v says nothing about v -> u), a mixture
  * of zeros, dust (2^-80 .. 2^-70) and weights of order 1, and GARBAGE -- large positive numbers -- on the padding voxels of partial
  * tiles and on every direction that leaves the volume.  Neither may raise a scale, open an arc, count as closed or carry a mark.
  * The floods run tile by tile the way the device runs them: a work list visited in RANDOM order, every visit queues neighbour tiles
- * (stamp de-duplicated) for the next pass, until a pass queues nobody.  The forward flood is the tile step of mgc_reach_ops.inl on
- * the thresholded plane, the backward flood the new step.  6 and 26 directions, partial tiles, single-voxel axes.
+ * (stamp de-duplicated) for the next pass, until a pass queues nobody.  Both floods are the tile step of mgc_reach_ops.inl on the
+ * thresholded plane, with the arcs and against them.  6 and 26 directions, partial tiles, single-voxel axes.
  *
  * Built and run by tests/test_cut_sets_tol_host.py, plainly and with -fsanitize=address,undefined.  Exit code 0 = all passed.
  */
-#include <algorithm>
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <queue>
-#include <random>
-#include <vector>
 
 #include "../../medpy_amd/csrc/mgc_reach_tol_ops.inl"
-
-struct NoBarrier {
-    int operator()(int v) const { return v; }
-};
-
-static MgcLattice lattice(int64_t dz, int64_t dy, int64_t dx, int ndir)
-{
-    MgcLattice L;
-    memset(&L, 0, sizeof(L));
-    L.dz = dz; L.dy = dy; L.dx = dx;
-    L.nvox = dz * dy * dx;
-    L.gz = (int)((dz + 7) / 8); L.gy = (int)((dy + 7) / 8); L.gx = (int)((dx + 7) / 8);
-    L.ntiles = L.gz * L.gy * L.gx;
-    L.tz_own_hi = L.gz;
-    L.ndir = ndir;
-    L.nshard = 1;
-    return L;
-}
+#include "reach_host.h"
 
 struct Result {
     int passes_fwd = 0, passes_back = 0;
     long closed = 0;
 };
-
-/* the neighbour of voxel id in direction d, or -1 */
-template <int NDIR>
-static int64_t neighbour(const MgcLattice& L, int64_t id, int d)
-{
-    int oz, oy, ox;
-    mgc_reach_offset<NDIR>(d, oz, oy, ox);
-    const int64_t x = id % L.dx + ox, y = (id / L.dx) % L.dy + oy, z = id / (L.dx * L.dy) + oz;
-    if (z < 0 || z >= L.dz || y < 0 || y >= L.dy || x < 0 || x >= L.dx) return -1;
-    return (z * L.dy + y) * L.dx + x;
-}
-
-/* one flood to its fixpoint, tile by tile; back = the new step, else the forward step of mgc_reach_ops.inl */
-template <int NDIR, class Mask>
-static int flood(const MgcLattice& L, std::vector<uint8_t>& marks, const std::vector<Mask>& masks, bool back, std::mt19937& rng, int& passes)
-{
-    std::vector<int> cur, nxt;
-    std::vector<uint32_t> stamp(L.ntiles, 0);
-    for (int tile = 0; tile < L.ntiles; ++tile)
-        for (int v = 0; v < MGC_TV; ++v)
-            if (marks[(size_t)tile * MGC_TV + v]) { cur.push_back(tile); break; }
-    std::vector<uint8_t> mk(MGC_REACH_BLOCK);
-    std::vector<uint32_t> ms(MGC_REACH_BLOCK);
-    NoBarrier sync;
-    uint32_t epoch = 0;
-    while (!cur.empty()) {
-        ++epoch;
-        if (++passes > 100000) { printf("the flood does not end\n"); return 1; }
-        std::shuffle(cur.begin(), cur.end(), rng);
-        for (int tile : cur) {
-            const uint32_t wake = back ? mgc_reach_tile_step_back<NDIR>(L, marks.data(), masks.data(), tile, mk.data(), ms.data(), 0, 1, sync)
-                                       : mgc_reach_tile_step<NDIR>(L, marks.data(), masks.data(), tile, mk.data(), ms.data(), 0, 1, sync);
-            for (int c = 0; c < 27; ++c) {
-                if (!((wake >> c) & 1u)) continue;
-                const int nt = mgc_reach_wake_tile(L, tile, c);
-                if (nt < 0) { printf("tile %d wakes a tile outside the grid (bit %d)\n", tile, c); return 1; }
-                if (stamp[nt] != epoch) { stamp[nt] = epoch; nxt.push_back(nt); }
-            }
-        }
-        cur.swap(nxt);
-        nxt.clear();
-    }
-    return 0;
-}
 
 template <int NDIR, class Mask>
 static int run_case(int64_t dz, int64_t dy, int64_t dx, double p_zero, double p_dust, double p_seed, double tol, uint32_t seed, Result& res)
@@ -189,8 +123,8 @@ static int run_case(int64_t dz, int64_t dy, int64_t dx, double p_zero, double p_
                 if (open) { ref[n] = 1; q.push(n); }
             }
         }
-        int& passes = back ? res.passes_back : res.passes_fwd;
-        if (flood<NDIR, Mask>(L, marks, masks, back != 0, rng, passes)) return 1;
+        long visits = 0;
+        if (flood<NDIR, Mask>(L, marks, masks, back != 0, rng, back ? res.passes_back : res.passes_fwd, visits)) return 1;
         long bad = 0, padding = 0, count = 0;
         for (size_t i = 0; i < ntv; ++i)
             if (marks[i] && !inside[i]) padding++;

@@ -1,5 +1,5 @@
-"""CPU tier of the cut sets at a rounding tolerance (mgc_cut_sets_tol): the scale, open and backward tile steps of
-mgc_reach_tol_ops.inl as a stand-alone host program against a per-voxel restatement and a voxel BFS; the pin that makes the GPU tier's
+"""CPU tier of the cut sets at a rounding tolerance (mgc_cut_sets_tol): the scale and open steps of
+mgc_reach_tol_ops.inl and both directions of the tile step of mgc_reach_ops.inl as a stand-alone host program against a per-voxel restatement and a voxel BFS; the pin that makes the GPU tier's
 expectations legitimate -- the device's RULE, restated in NumPy over BK's residual graph of the dusty graph, gives at 64 ulp the tol-0 sets
 of the clean graph, for every case and seed the GPU tier uses; header, symbol table and library agree on the two new calls; the Python
 surface that needs no device."""
@@ -111,20 +111,31 @@ def test_header_table_and_library_agree_on_the_new_calls():
         res, args = _lib.SIGNATURES[name]
         assert res is ctypes.c_int and len(args) == decl.count(",") + 1
     assert _lib.SIGNATURES["mgc_cut_sets_tol"][1][1] is ctypes.c_double
-    for d in ("mgc_reach_tol_ops.inl", "mgc_reach_tol.h"):
+    for d in ("mgc_reach_ops.inl", "mgc_reach_tol_ops.inl", "mgc_reach_tol.h", "mgc_reach_driver.inl"):
         assert d in build.DEPS and os.path.exists(os.path.join(build.CSRC, d)), d
     # the rule is stated once, in the header that host code compiles; the steps are what the host program compiles
     rule = open(os.path.join(build.CSRC, "mgc_reach_tol.h")).read()
     assert "mgc_tol_arc_open" in rule and "mgc_tol_tlink_open" in rule and "__global__" not in rule and "hip_runtime" not in rule
     text = open(os.path.join(build.CSRC, "mgc_reach_tol_ops.inl")).read()
     host_part = text[:text.index("#if defined(__HIPCC__)")]
-    assert "mgc_reach_tile_step_back" in host_part and "__global__" not in host_part and "hip_runtime" not in text
-    # the backward path consults neither labels nor summaries
-    back = text[text.index("void k_reach_flood_back"):text.index("void k_reach_readout_tol")] + host_part
+    assert "mgc_reach_open_tile" in host_part and "__global__" not in host_part and "hip_runtime" not in text
+    # one tile step and one flood kernel serve both directions; they live in mgc_reach_ops.inl, the back forms are gone
+    step = open(os.path.join(build.CSRC, "mgc_reach_ops.inl")).read()
+    step_host = step[:step.index("#if defined(__HIPCC__)")]
+    assert "template <int NDIR, bool BACK = false, class Mask, class Sync>" in step_host and "__global__" not in step_host and "hip_runtime" not in step
+    assert step.count("uint32_t mgc_reach_tile_step(") == 1 and step.count("void k_reach_flood(") == 1
+    for gone in ("mgc_reach_tile_step_back", "k_reach_flood_back"):
+        assert gone not in step and gone not in text, gone
+    # the backward path consults neither labels nor summaries: the code of the step and of the flood kernel (header comment apart),
+    # the host part of the tol file, the backward seeding's arguments
+    back = step_host[step_host.index("MGC_HD bool mgc_reach_pull("):] + step[step.index("void k_reach_flood("):step.index("void k_reach_readout(")] + host_part
     assert "height" not in back and "tsum" not in back and "d_labels" not in back
-    # ... and the kernel file ends on the new code: nothing of the solve moved in the code object
+    # ... and the kernel file ends on the one include that brings the reach code in: nothing of the solve moved in the code object
     kernels = open(os.path.join(build.CSRC, "mgc_kernels.hip")).read()
-    assert kernels.index('#include "mgc_reach_tol_ops.inl"') > kernels.index("int mgc_get_stats(") > kernels.index('#include "mgc_reach_ops.inl"')
+    assert kernels.rstrip().endswith('#include "mgc_reach_driver.inl"') and kernels.index('#include "mgc_reach_driver.inl"') > kernels.index("int mgc_get_stats(")
+    assert "mgc_reach" not in kernels.replace('#include "mgc_reach_driver.inl"', "")
+    driver = open(os.path.join(build.CSRC, "mgc_reach_driver.inl")).read()
+    assert driver.count('#include "mgc_reach_ops.inl"') == 1 and driver.count('#include "mgc_reach_tol_ops.inl"') == 1
 
 
 class _Recorder(object):
