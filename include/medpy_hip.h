@@ -332,6 +332,38 @@ int mgc_update_tweights(mgc_handle h, const void* source, const void* sink, int 
 int mgc_edit_tweights(mgc_handle h, int64_t n, const int64_t* ids, const double* source, const double* sink);
 int mgc_get_tweight_edit_info(mgc_handle h, int64_t* out4);
 
+/* The binned regional term: t-links that depend on a voxel only through the BIN of its intensity -- the negative log-likelihoods
+ * of the intensity histograms under the markers (Boykov & Jolly), of a mixture model evaluated per bin, any table; DESIGN 14.
+ * What a stroke changes of such a term is two tables of a few hundred entries, so the term is fitted and expanded on the device:
+ * no per-voxel array crosses the bus.
+ *   The rule (medpy_amd/csrc/mgc_binned.h): bin(v) = clamp(floor((double(v) - lo) / width), 0, nbins - 1), one f64 subtraction,
+ * one IEEE f64 division and a floor, bit for bit numpy.clip(numpy.floor((image.astype(float64) - lo) / width), 0, nbins - 1).
+ * 1 <= nbins <= 65536, lo finite, width finite and > 0.
+ *   mgc_set_feature_image: the scalar image the bins are taken of, a C-contiguous array of the handle's shape in any image dtype
+ * (MGC_U8 .. MGC_F64), uploaded and kept with the handle (counted in device_bytes); NULL forgets it and gives the bytes back.
+ * Where none is set the calls below read the image of mgc_set_boundary (the maximum_* terms take a gradient image: then a feature
+ * image is needed).  No effect on mgc_build or on any other call; a built handle stays built.
+ *   mgc_marker_histograms: fg_hist[b] / bg_hist[b] (nbins entries each) = the voxels of bin b under the fg plane / under the bg
+ * plane the handle holds now (mgc_set_markers, mgc_update_markers, mgc_edit_markers); a voxel under both counts in both, a
+ * plane that was never given counts nothing.  out4 (or NULL) = {counts under fg, counts under bg, counts the clamp raised into
+ * bin 0 (value below lo), counts the clamp lowered into the last bin (value at or above lo + nbins * width)}.  Exact integers,
+ * whatever the order of the adds.  Valid before and after mgc_build; changes nothing on the handle.
+ *   mgc_add_tweights_binned: leaves the store exactly as mgc_add_tweights(h, S, K, MGC_F64) would with S[p] = source_table[bin(p)]
+ * and K[p] = sink_table[bin(p)] -- the same add_tweights on top of what the store holds, the same share plane, the same
+ * fixed-order flow constant, the same count of dense calls, the same states, and a note of where its time went (check_ms,
+ * expand_ms, flow_const_ms) in mgc_last_error.  mgc_update_tweights_binned: the warm form, exactly mgc_update_tweights of the
+ * expanded arrays (the store replaced, the changed voxels counted, the change folded into the residual graph, the label
+ * snapshot dropped; its states); its note adds fold_ms.
+ *   Refusals, all before anything is written, the handle exactly as it was: MGC_ERR_INVALID for nbins, lo or width out of range,
+ * a NULL table, a table entry that is not finite (negative entries are allowed; mgc_last_error names table and index) and a value
+ * of a float image that is not finite (flat index and value; mgc_marker_histograms looks only under the markers);
+ * MGC_ERR_STATE without a feature image and without a boundary image, and in the states of mgc_add_tweights /
+ * mgc_update_tweights; MGC_ERR_UNSUPPORTED on a slab handle; MGC_ERR_OOM before anything changed. */
+int mgc_set_feature_image(mgc_handle h, const void* image, int dtype);
+int mgc_marker_histograms(mgc_handle h, int64_t nbins, double lo, double width, int64_t* fg_hist, int64_t* bg_hist, int64_t* out4);
+int mgc_add_tweights_binned(mgc_handle h, int64_t nbins, double lo, double width, const double* source_table, const double* sink_table);
+int mgc_update_tweights_binned(mgc_handle h, int64_t nbins, double lo, double width, const double* source_table, const double* sink_table);
+
 /* Runs the n-link / t-link kernels: the residual graph is now resident in HBM. */
 int mgc_build(mgc_handle h);
 

@@ -45,6 +45,8 @@ class Stats(C.Structure):
 
 OP_FIRST_RELABEL = 9  # mgc_solver_op: the first global relabel by distance transform alone (MGC_OP_FIRST_RELABEL)
 HINF = 0x3f3f3f3f     # the label "cannot reach the sink" (MGC_HINF)
+BINNED_MAX_BINS = 65536  # most bins of the binned regional term (MGC_BINNED_MAX_BINS, medpy_amd/csrc/mgc_binned.h)
+BINNED_LDS_MAX = 4096    # up to this many bins mgc_marker_histograms counts in LDS, above it in device memory (MGC_BINNED_LDS_MAX)
 
 # mgc_get_launch_counts: the kinds of solver launch, in the order of MGC_LAUNCH_* (include/medpy_hip.h)
 LAUNCH_KINDS = ("k_discharge", "k_discharge_w", "k_relabel_tile", "k_relabel_v", "k_relabel_w", "k26_discharge", "k26_discharge_v", "k26_discharge_w",
@@ -150,6 +152,10 @@ SIGNATURES = {
     "mgc_update_tweights": (_INT, [_VP, _VP, _VP, _INT]),
     "mgc_edit_tweights": (_INT, [_VP, _I64, _VP, _VP, _VP]),
     "mgc_get_tweight_edit_info": (_INT, [_VP, _VP]),
+    "mgc_set_feature_image": (_INT, [_VP, _VP, _INT]),
+    "mgc_marker_histograms": (_INT, [_VP, _I64, _DBL, _DBL, _VP, _VP, _VP]),
+    "mgc_add_tweights_binned": (_INT, [_VP, _I64, _DBL, _DBL, _VP, _VP]),
+    "mgc_update_tweights_binned": (_INT, [_VP, _I64, _DBL, _DBL, _VP, _VP]),
     "mgc_build": (_INT, [_VP]),
     "mgc_get_nweights": (_INT, [_VP, _INT, _VP]),
     "mgc_get_tweights": (_INT, [_VP, _VP]),

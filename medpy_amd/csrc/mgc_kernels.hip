@@ -2874,6 +2874,9 @@ struct mgc_graph {
     bool converged = false;    /* `solved` was set by an mgc_maxflow whose schedule ended on "no active tile" (mgc_finish cannot know): what mgc_cut_sets asks for */
     int64_t cut_info[8] = {0, 0, 0, 0, 0, 0, 0, 0}; double cut_source = 0.0; bool cut_info_valid = false; /* of the last mgc_cut_sets (mgc_get_cut_sets_info) */
     int64_t cut_tol_info[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; double cut_tol_vals[4] = {0.0, 0.0, 0.0, 0.0}; bool cut_tol_info_valid = false; /* of the last mgc_cut_sets_tol */
+    /* the scalar feature image of the binned regional term (mgc_set_feature_image, mgc_binned_driver.inl), kept the way
+       mgc_upload keeps d_image; none: the binned calls read d_image */
+    void* d_feat = nullptr; int feat_dtype = 0;
 };
 
 static int mgc_fail(mgc_handle h, int code, const char* fmt, ...)
@@ -4266,6 +4269,7 @@ int mgc_destroy(mgc_handle h)
                     h->d_labels, h->d_labels_prev, h->d_tflags, h->d_tsum, h->d_image, h->d_lut, h->d_lut_new, h->d_prob, h->d_fg, h->d_bg, h->d_tr_in, h->d_tw_part, h->d_eslot, h->d_eval, h->d_erun, h->d_dense, (void*)h->d_dense_planes, L.hshadow[0], L.hshadow[1], h->d_vout, h->d_dt16, h->d_ds16, h->d_hexact, h->d_halo, h->d_xchg[0], h->d_xchg[1], h->d_xchg[2], h->d_xchg[3], h->d_cnt64, h->d_carry[0], h->d_carry[1], h->d_carry_in[0], h->d_carry_in[1]};
     for (void* p : ptrs)
         if (p) (void)mgc_dfree(p);
+    if (h->d_feat) (void)mgc_dfree(h->d_feat);
     for (auto& planes : h->dense_extra)
         for (double* p : planes) (void)mgc_dfree(p);
     if (h->h_count) (void)hipHostFree(h->h_count);

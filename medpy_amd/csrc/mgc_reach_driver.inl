@@ -315,3 +315,6 @@ int mgc_get_cut_sets_tol_info(mgc_handle h, int64_t* out16, double* out4)
 }
 
 } /* extern "C" */
+
+/* (behind the kernels of this file as well: the binned regional term, DESIGN 14 -- the last code of the library) */
+#include "mgc_binned_driver.inl"

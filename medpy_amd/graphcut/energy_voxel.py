@@ -17,7 +17,7 @@ __all__ = [
     "boundary_maximum_exponential", "boundary_difference_exponential",
     "boundary_maximum_division", "boundary_difference_division",
     "boundary_maximum_power", "boundary_difference_power",
-    "boundary_precomputed", "regional_precomputed",
+    "boundary_precomputed", "regional_precomputed", "regional_histogram",
 ]
 
 
@@ -122,3 +122,16 @@ def regional_precomputed(graph, xxx_todo_changeme10):
     (weights_source, weights_sink) = xxx_todo_changeme10
     _need_facade(graph)
     graph.set_tweights_dense(weights_source, weights_sink)
+
+
+def regional_histogram(graph, xxx_todo_changeme11):
+    """Regional term of interactive graph cut (Boykov & Jolly; extension, no reference counterpart): the intensity histograms of
+    the voxels under the foreground and under the background markers give every voxel the t-links ``-lam * ln Pr(I_p | bkg)``
+    (source) and ``-lam * ln Pr(I_p | obj)`` (sink).  ``image``: an array of the volume's shape; ``bins``: None for one bin per
+    value of an integer image, else the number of equal bins between its minimum and maximum; ``lam`` weighs the term against
+    the boundary term, ``eps`` (> 0) is added to every count.  ``medpy_amd.graphcut.histogram`` is the definition of the term.
+    On the tile solver histograms and t-links are computed on the device from the resident image and markers, and
+    ``VoxelGraph.refit_regional_histogram()`` fits the term again after ``edit_markers``."""
+    (image, bins, lam, eps) = xxx_todo_changeme11
+    _need_facade(graph)
+    graph.record_regional_histogram(image, bins, lam, eps)

@@ -12,6 +12,8 @@ import enum
 import numpy
 
 from .. import _lib
+from . import histogram as _histogram
+from .histogram import histogram_binning, histogram_bins, histogram_tables   # noqa: F401  (the definition of the histogram regional term)
 
 
 ULP64 = 64 * 2.0 ** -52   # the rounding granularity of the project's parity statement, for the ``tol`` of VoxelGraph.source_side & co.
@@ -288,6 +290,21 @@ def _dense_tweight_arrays(shape, weights_source, weights_sink):
     return numpy.ascontiguousarray(out[0]), numpy.ascontiguousarray(out[1])
 
 
+class _HistogramTerm(object):
+    """what ``GCGraph.record_regional_histogram`` records: the image (in the volume's shape), its binning and the two parameters"""
+    __slots__ = ("image", "nbins", "lo", "width", "lam", "eps")
+
+    def __init__(self, image, nbins, lo, width, lam, eps):
+        self.image, self.nbins, self.lo, self.width, self.lam, self.eps = image, nbins, lo, width, lam, eps
+
+
+def _same_array(a, b):
+    """do two arrays view the same memory in the same way (is ``a`` the array ``b`` already went up as)?"""
+    a, b = numpy.asarray(a), numpy.asarray(b)
+    return a is b or (a.shape == b.shape and a.dtype == b.dtype and a.strides == b.strides
+                      and a.__array_interface__["data"][0] == b.__array_interface__["data"][0])
+
+
 def pad_skeleton_weights(shape, axis, weights):
     """The per-axis weight array of the reference's ``__skeleton_base`` (energy_voxel.py:644-658: extent - 1 along ``axis``, entry p =
     the pair (p, p + e_axis)) as an array of the full ``shape``: the same entries, and one more slice along ``axis`` that holds
@@ -361,6 +378,11 @@ class VoxelGraph(object):
     Is the cut unique?  After ``maxflow()``, ``source_side()`` is the source side of the SMALLEST minimum cut (``labels()`` is that
     of the largest), ``ambiguous()`` the voxels between the two -- some minimum cut has them on either side -- ``cut_is_unique()``
     whether there are none, ``cut_sets_info()`` the counts; one forward flood of the residual graph on the device.
+
+    The histogram regional term (``energy_voxel.regional_histogram``) moves with every stroke: ``refit_regional_histogram()`` counts
+    the intensities under the markers as they stand now on the device, turns the two histograms into two tables on the host and
+    expands them into the t-links on the device; ``marker_histograms()`` and ``update_tweights_binned(source_table, sink_table)``
+    are its two halves, for terms of the caller's own over the same bins.
     """
 
     termtype = termtype
@@ -607,6 +629,98 @@ class VoxelGraph(object):
         self._call("mgc_edit_tweights", ids.size, _lib.ptr(ids), _lib.ptr(source), _lib.ptr(sink))
         if ids.size:
             self._labels = None
+
+    # -- the binned regional term: histograms of the markers, tables expanded on the device
+    _binning = None        # (nbins, lo, width) the graph was built with (GCGraph.record_regional_histogram)
+    _hist_params = None    # (lam, eps) of that term
+    _hist_counts = None    # out4 of the last marker_histograms
+
+    def _set_feature_image(self, image):
+        """mgc_set_feature_image: the scalar image the bins are taken of where it is not the boundary term's own (None forgets it)"""
+        if image is None:
+            self._call("mgc_set_feature_image", None, 0)
+            return
+        image = _device_image(image)
+        self._check_volume_shape(image, "feature image")
+        self._call("mgc_set_feature_image", _lib.ptr(image), _lib.DTYPE_IDS[image.dtype])
+
+    def _binned_args(self, what, nbins, lo, width):
+        given = [v is not None for v in (nbins, lo, width)]
+        if not any(given):
+            if self._binning is None:
+                raise ValueError("%s: the graph was built without a histogram term: pass nbins, lo and width" % what)
+            return self._binning
+        if not all(given):
+            raise ValueError("%s: nbins, lo and width come together" % what)
+        return _histogram._check_binning(nbins, lo, width)
+
+    @staticmethod
+    def _binned_tables(what, nbins, source_table, sink_table):
+        tables = [numpy.ascontiguousarray(t, dtype=numpy.float64) for t in (source_table, sink_table)]
+        for t in tables:
+            if t.ndim != 1 or t.size != nbins:
+                raise ValueError("%s: a table of shape %s for %d bins" % (what, t.shape, nbins))
+        return tables
+
+    def marker_histograms(self, nbins=None, lo=None, width=None):
+        """``(fg_hist, bg_hist)``: per bin the voxels under the foreground and under the background markers the graph holds now
+        (after ``edit_markers`` / ``update_markers`` too), int64 arrays of ``nbins`` entries, counted on the device
+        (mgc_marker_histograms) -- exactly ``numpy.bincount(histogram_bins(image, nbins, lo, width)[mask], minlength=nbins)``.  The
+        image is the feature image of the graph or, where none was set, the boundary term's.  No arguments: the binning the graph
+        was built with.  ``marker_histogram_info()`` has the totals of this call."""
+        nbins, lo, width = self._binned_args("marker_histograms", nbins, lo, width)
+        fg = numpy.zeros(nbins, dtype=numpy.int64)
+        bg = numpy.zeros(nbins, dtype=numpy.int64)
+        out4 = numpy.zeros(4, dtype=numpy.int64)
+        self._call("mgc_marker_histograms", nbins, lo, width, _lib.ptr(fg), _lib.ptr(bg), _lib.ptr(out4))
+        self._hist_counts = out4
+        return fg, bg
+
+    def marker_histogram_info(self):
+        """of the last ``marker_histograms``: counts under the foreground markers, under the background markers, counts whose value
+        lay below ``lo`` (clamped into bin 0) and at or above ``lo + nbins * width`` (clamped into the last bin)"""
+        out4 = self._hist_counts if self._hist_counts is not None else numpy.zeros(4, dtype=numpy.int64)
+        return dict(zip(("fg_voxels", "bg_voxels", "below", "above"), out4.tolist()))
+
+    def _add_tweights_binned(self, source_table, sink_table, nbins, lo, width):
+        """mgc_add_tweights_binned: one ``add_tweights(source_table[bin(p)], sink_table[bin(p)])`` per voxel on the graph's explicit
+        t-links -- what ``_add_tweights(source_table[bins], sink_table[bins])`` with ``bins = histogram_bins(image, nbins, lo, width)``
+        leaves, without the two arrays"""
+        nbins, lo, width = _histogram._check_binning(nbins, lo, width)
+        source, sink = self._binned_tables("_add_tweights_binned", nbins, source_table, sink_table)
+        self._labels = None
+        self._call("mgc_add_tweights_binned", nbins, lo, width, _lib.ptr(source), _lib.ptr(sink))
+
+    def update_tweights_binned(self, source_table, sink_table, nbins=None, lo=None, width=None):
+        """Replace the explicit t-links by ``source_table[bin(p)]`` / ``sink_table[bin(p)]`` -- what
+        ``update_tweights_dense(source_table[bins], sink_table[bins])`` leaves, bit for bit, with the tables expanded on the device
+        -- and keep the residual graph: the next ``maxflow()`` is a warm solve.  ``nbins``, ``lo``, ``width`` of None: the binning
+        the graph was built with.  The carrier of any regional term that depends on a voxel through its bin: smoothed histograms, a
+        mixture model evaluated per bin.  MedpyHipError (ERR_INVALID) names the first table entry that is not finite; the graph is
+        then as it was."""
+        self._refuse_host_merged("update_tweights_binned")
+        nbins, lo, width = self._binned_args("update_tweights_binned", nbins, lo, width)
+        source, sink = self._binned_tables("update_tweights_binned", nbins, source_table, sink_table)
+        self._labels = None
+        self._call("mgc_update_tweights_binned", nbins, lo, width, _lib.ptr(source), _lib.ptr(sink))
+
+    def refit_regional_histogram(self, lam=None, eps=None):
+        """Fit the histogram regional term (``energy_voxel.regional_histogram``) to the markers as they stand now: the histograms
+        of the intensities under the two kinds of marker are counted on the device, ``histogram_tables`` turns them into the two
+        tables on the host, ``update_tweights_binned`` expands those into the graph's t-links.  ``lam`` / ``eps`` of None: those
+        the graph was built with.  Returns ``(fg_hist, bg_hist)``.  The next ``maxflow()`` is a warm solve with the labels and the
+        flow of a graph built from the markers and the refitted term; ``labels(out=previous)`` brings a copy of the previous labels
+        up to date."""
+        self._refuse_host_merged("refit_regional_histogram")
+        if self._binning is None or self._hist_params is None:
+            raise ValueError("refit_regional_histogram: the graph was built without a histogram term (energy_voxel.regional_histogram)")
+        lam = self._hist_params[0] if lam is None else lam
+        eps = self._hist_params[1] if eps is None else eps
+        fg_hist, bg_hist = self.marker_histograms()
+        source_table, sink_table = histogram_tables(fg_hist, bg_hist, lam, eps)
+        self.update_tweights_binned(source_table, sink_table)
+        self._hist_params = (lam, eps)
+        return fg_hist, bg_hist
 
     def _add_nweights(self, offset, there, back=None):
         """mgc_add_nweights: ``there[p]`` is added to the arc p -> p + offset, ``back[p]`` (None: ``there[p]``) to the arc
@@ -1689,7 +1803,9 @@ class GCGraph(object):
         self.__edge_i, self.__edge_j, self.__edge_w, self.__edge_r = [], [], [], []
         self.__dense = []  # (offset, there, back or None): whole n-link weight arrays, in call order (set_nweights_dense)
         self.__tr = None  # merged explicit t-links (graph.h:416-425 applied call by call)
-        self.__tdense = []  # (source, sink): whole t-link weight arrays, in call order (set_tweights_dense), while no per-node t-weight exists
+        self.__tdense = []  # (source, sink): whole t-link weight arrays, in call order (set_tweights_dense), while no per-node t-weight exists;
+        #                     (_HistogramTerm, None): a histogram term (record_regional_histogram), fitted when the markers are known
+        self.__markers_recorded = False
         self.__flow_const = 0.0
         self.__graph = None
         self.__lattice_shape = None  # set when the boundary image has another shape than the markers
@@ -1735,10 +1851,36 @@ class GCGraph(object):
             raise ValueError("probability map holds {} values for {} nodes".format(pm.size, self.__nodes))
         self.__regional = (pm.reshape(self.__shape), alpha)
 
+    def record_regional_histogram(self, image, bins=None, lam=1.0, eps=0.5):
+        """The histogram regional term (``energy_voxel.regional_histogram``; medpy_amd/graphcut/histogram.py is its definition):
+        the intensities of ``image`` under the foreground and the background markers are counted in the bins of
+        ``histogram_binning(image, bins)``, and voxel p gets ``set_tweight(p, source_table[bin(p)], sink_table[bin(p)])`` with the
+        tables of ``histogram_tables(fg_hist, bg_hist, lam, eps)``.  The term is FITTED WHEN THE GRAPH IS BUILT, on the markers known
+        then, and keeps its place in call order among the dense t-link calls.  On a graph of the tile solver whose explicit
+        t-links are nothing but dense calls the histograms are counted and the tables expanded on the device
+        (mgc_marker_histograms, mgc_add_tweights_binned), and ``VoxelGraph.refit_regional_histogram`` fits the term again after a
+        stroke; every other graph evaluates the same term on the host and merges it like ``set_tweights_dense``.  ValueError for an
+        image of another size, a value that is not finite, bad ``bins``, ``lam`` or ``eps``, before anything is recorded."""
+        image = numpy.asarray(image)
+        if image.size != self.__nodes:
+            raise ValueError("histogram image holds {} values for {} nodes".format(image.size, self.__nodes))
+        nbins, lo, width = histogram_binning(image, bins)
+        histogram_tables(numpy.zeros(1), numpy.zeros(1), lam, eps)   # (lam and eps are checked here, before anything is recorded)
+        if self.__graph is not None:
+            raise NotImplementedError("medpy_amd: the graph is built already: VoxelGraph.refit_regional_histogram / update_tweights_binned change its t-links")
+        self.__tdense.append((_HistogramTerm(image.reshape(self.__shape), nbins, lo, width, float(lam), float(eps)), None))
+
+    def __histogram_arrays(self, term):
+        """the two per-voxel arrays of a histogram term, evaluated on the host on the markers known now"""
+        fg_hist, bg_hist, bins = _histogram.marker_histograms(term.image, self.__fg, self.__bg, term.nbins, term.lo, term.width)
+        source_table, sink_table = histogram_tables(fg_hist, bg_hist, term.lam, term.eps)
+        return source_table[bins], sink_table[bins]
+
     # -- reference API
     def record_markers(self, fg_mask, bg_mask):
         """fast path of ``graph_from_voxels``: the marker MASKS (bool arrays of the volume's shape) instead of id lists --
         what ``set_source_nodes(flatnonzero(fg))`` / ``set_sink_nodes(flatnonzero(bg))`` would leave, without the lists"""
+        self.__markers_recorded = True
         for mask, side in ((fg_mask, "fg"), (bg_mask, "bg")):
             mask = numpy.ascontiguousarray(mask, dtype=numpy.bool_)
             if mask.size != self.__nodes:
@@ -1860,16 +2002,21 @@ class GCGraph(object):
         source, sink = _dense_tweight_arrays(self.__shape, weights_source, weights_sink)
         if self.__graph is not None:
             raise NotImplementedError("medpy_amd: the graph is built already: VoxelGraph.update_tweights_dense / edit_tweights change its t-links")
-        if self.__tr is not None:   # per-node t-weights exist: this call comes after them
+        if self.__tr is not None and not self.__tdense:   # per-node t-weights exist: this call comes after them
             self.merge_tweights(numpy.arange(self.__nodes), source.ravel(), sink.ravel())
-        else:
+        else:   # (behind a histogram term that waits for the markers the call waits too: call order)
             self.__tdense.append((source, sink))
 
     def __merge_dense_tweights(self):
         """the recorded dense calls, merged on the host in call order (a per-node t-weight follows, or the graph goes to a solver
-        that takes one merged vector)"""
+        that takes one merged vector); a histogram term among them is fitted to the markers known now"""
+        if any(sink is None for _, sink in self.__tdense) and self.__fg is None and self.__bg is None and not self.__markers_recorded:
+            raise NotImplementedError("medpy_amd: a per-node t-weight behind a histogram regional term, before the markers are known: "
+                                      "the term is fitted to the markers; set the markers first")
         calls, self.__tdense = self.__tdense, []
         for source, sink in calls:
+            if sink is None:
+                source, sink = self.__histogram_arrays(source)
             self.merge_tweights(numpy.arange(self.__nodes), source.ravel(), sink.ravel())
 
     def set_tweights(self, tweights):
@@ -1906,8 +2053,8 @@ class GCGraph(object):
             self.__general = True  # a plug-in term added an edge between voxels that are not neighbours
         if self.__graph is None and self.__dense and (self.__general or self.__lattice_shape is not None):
             raise NotImplementedError("medpy_amd: dense n-link weight arrays on a graph that goes to the sparse-graph solver")
-        if self.__graph is None and self.__tdense and (self.__general or self.__lattice_shape is not None):
-            self.__merge_dense_tweights()   # (these solvers take one merged vector)
+        if self.__graph is None and self.__tdense and (self.__general or self.__lattice_shape is not None or self.__tr is not None):
+            self.__merge_dense_tweights()   # (these solvers take one merged vector; so does a graph that holds per-node t-weights)
         if self.__graph is None and self.__general:
             self.__graph = self.__sparse_graph()
         if self.__graph is None and self.__lattice_shape is not None:
@@ -1921,9 +2068,27 @@ class GCGraph(object):
                 g._set_regional(*self.__regional)
             if self.__tr is not None:
                 g._set_tweights_merged(self.__tr, self.__flow_const)
+            fitted = any(sink is None for _, sink in self.__tdense)   # a histogram term: the markers go up before it is fitted to them
+            if fitted and (self.__fg is not None or self.__bg is not None):
+                g._set_markers(None if self.__fg is None else self.__fg, None if self.__bg is None else self.__bg)
+            feature = None   # the feature image resident on the handle (None: the calls read the boundary term's)
             for source, sink in self.__tdense:   # (nothing but dense calls: __tr is None)
-                g._add_tweights(source, sink)
-            if self.__fg is not None or self.__bg is not None:
+                if sink is not None:
+                    g._add_tweights(source, sink)
+                    continue
+                term = source   # counted and expanded on the device, in its place in call order
+                own = self.__boundary is not None and _same_array(term.image, self.__boundary[1])
+                if not own and (feature is None or not _same_array(term.image, feature)):
+                    g._set_feature_image(term.image)
+                    feature = term.image
+                elif own and feature is not None:
+                    g._set_feature_image(None)
+                    feature = None
+                fg_hist, bg_hist = g.marker_histograms(term.nbins, term.lo, term.width)
+                source_table, sink_table = histogram_tables(fg_hist, bg_hist, term.lam, term.eps)
+                g._add_tweights_binned(source_table, sink_table, term.nbins, term.lo, term.width)
+                g._binning, g._hist_params = (term.nbins, term.lo, term.width), (term.lam, term.eps)
+            if not fitted and (self.__fg is not None or self.__bg is not None):
                 g._set_markers(None if self.__fg is None else self.__fg, None if self.__bg is None else self.__bg)
             for off, there, back in self.__dense:   # (after the boundary term, before the explicit edges: the order mgc_build applies them in)
                 g._add_nweights(off, there, back)
