@@ -364,6 +364,21 @@ int mgc_marker_histograms(mgc_handle h, int64_t nbins, double lo, double width, 
 int mgc_add_tweights_binned(mgc_handle h, int64_t nbins, double lo, double width, const double* source_table, const double* sink_table);
 int mgc_update_tweights_binned(mgc_handle h, int64_t nbins, double lo, double width, const double* source_table, const double* sink_table);
 
+/* The histograms of EVERY voxel, split by a label: what fitting the binned term to a segmentation instead of the strokes needs (the
+ * iterated graph cut of GrabCut).  fg_hist[b] / bg_hist[b] (nbins entries each) = the voxels of bin b whose label is not
+ * zero / is zero; the image and the rule of the bin are those of mgc_marker_histograms.  out4 (or NULL) = {voxels with a label,
+ * voxels without, counts the clamp raised into bin 0, counts the clamp lowered into the last bin}.  Exact integers, whatever the
+ * order of the adds: numpy.bincount of the bins under the labels and under their complement.
+ *   labels NULL: the labels of the handle's current cut, read where they lie on the device -- valid in the states of mgc_cut_sets
+ * (built, solved to a maximum preflow, no update or edit waiting for the next mgc_maxflow), MGC_ERR_STATE otherwise.  labels given:
+ * one byte per voxel in C order on the host, not zero = foreground; the plane goes up into a block that is given back before the
+ * call returns, and the call is valid wherever the handle holds an image, before mgc_build too.
+ *   Refusals, all before anything is written: MGC_ERR_INVALID for nbins, lo or width out of range, for fg_hist or bg_hist NULL and
+ * for a value of a float image that is not finite ANYWHERE in the volume (the lowest flat index and the value are named: every
+ * voxel is counted here); MGC_ERR_STATE without a feature image and without a boundary image; MGC_ERR_UNSUPPORTED on a slab
+ * handle.  Changes nothing on the handle: labels, label snapshot, residual graph, statistics, launch counts and device_bytes stay. */
+int mgc_label_histograms(mgc_handle h, const uint8_t* labels, int64_t nbins, double lo, double width, int64_t* fg_hist, int64_t* bg_hist, int64_t* out4);
+
 /* Runs the n-link / t-link kernels: the residual graph is now resident in HBM. */
 int mgc_build(mgc_handle h);
 

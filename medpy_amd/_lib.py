@@ -156,6 +156,7 @@ SIGNATURES = {
     "mgc_marker_histograms": (_INT, [_VP, _I64, _DBL, _DBL, _VP, _VP, _VP]),
     "mgc_add_tweights_binned": (_INT, [_VP, _I64, _DBL, _DBL, _VP, _VP]),
     "mgc_update_tweights_binned": (_INT, [_VP, _I64, _DBL, _DBL, _VP, _VP]),
+    "mgc_label_histograms": (_INT, [_VP, _VP, _I64, _DBL, _DBL, _VP, _VP, _VP]),
     "mgc_build": (_INT, [_VP]),
     "mgc_get_nweights": (_INT, [_VP, _INT, _VP]),
     "mgc_get_tweights": (_INT, [_VP, _VP]),

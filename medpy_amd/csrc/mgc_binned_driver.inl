@@ -225,3 +225,6 @@ int mgc_update_tweights_binned(mgc_handle h, int64_t nbins, double lo, double wi
 }
 
 } /* extern "C" */
+
+/* (behind the kernels of this file as well: the histograms over every voxel, DESIGN 15 -- the last code of the library) */
+#include "mgc_label_hist_driver.inl"

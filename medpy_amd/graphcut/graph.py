@@ -722,6 +722,80 @@ class VoxelGraph(object):
         self._hist_params = (lam, eps)
         return fg_hist, bg_hist
 
+    # -- the term fitted to the cut instead of the strokes
+    _label_hist_counts = None    # out4 of the last label_histograms
+
+    def label_histograms(self, labels=None, nbins=None, lo=None, width=None):
+        """``(fg_hist, bg_hist)``: per bin the voxels of the foreground and of the background of a segmentation, EVERY voxel in one
+        of the two, int64 arrays of ``nbins`` entries, counted on the device (mgc_label_histograms) -- exactly
+        ``numpy.bincount(bins[labels], minlength=nbins)`` and ``numpy.bincount(bins[~labels], minlength=nbins)`` with
+        ``bins = histogram_bins(image, nbins, lo, width)``.  ``labels`` of None: the labels of the graph's current cut, read where
+        they lie on the device (MedpyHipError ERR_STATE unless a converged ``maxflow()`` is current: not before the first solve, not
+        between an update or edit and the next ``maxflow()``).  Otherwise a bool or uint8 array of the volume's shape, not zero =
+        foreground; it goes up for this call only, and the call then works before the graph is built too.  Image and binning as in
+        ``marker_histograms``.  Nothing on the graph changes.  ``label_histogram_info()`` has the totals of this call."""
+        nbins, lo, width = self._binned_args("label_histograms", nbins, lo, width)
+        plane = None
+        if labels is not None:
+            if not (isinstance(labels, numpy.ndarray) and labels.dtype in (numpy.bool_, numpy.uint8) and labels.shape == self._shape):
+                raise ValueError("label_histograms: labels must be None or a bool / uint8 array of shape %s" % (self._shape,))
+            plane = self._marker_bytes(labels)
+        fg = numpy.zeros(nbins, dtype=numpy.int64)
+        bg = numpy.zeros(nbins, dtype=numpy.int64)
+        out4 = numpy.zeros(4, dtype=numpy.int64)
+        self._call("mgc_label_histograms", None if plane is None else _lib.ptr(plane), nbins, lo, width, _lib.ptr(fg), _lib.ptr(bg), _lib.ptr(out4))
+        self._label_hist_counts = out4
+        return fg, bg
+
+    def label_histogram_info(self):
+        """of the last ``label_histograms``: voxels of the foreground, of the background, counts whose value lay below ``lo``
+        (clamped into bin 0) and at or above ``lo + nbins * width`` (clamped into the last bin)"""
+        out4 = self._label_hist_counts if self._label_hist_counts is not None else numpy.zeros(4, dtype=numpy.int64)
+        return dict(zip(("fg_voxels", "bg_voxels", "below", "above"), out4.tolist()))
+
+    def iterate_regional_histogram(self, max_refits=8, lam=None, eps=None, stop_below=0):
+        """The iterated graph cut of GrabCut on the histogram regional term (``energy_voxel.regional_histogram``): fit the two
+        histograms to the CURRENT CUT instead of the strokes (``label_histograms()``), turn them into the two tables
+        (``histogram_tables``), expand those into the t-links (``update_tweights_binned``), solve warm -- and again, until the
+        histograms stop moving or ``max_refits`` refits are done.  Needs a converged ``maxflow()`` to start from (MedpyHipError
+        ERR_STATE otherwise).  The markers stay hard constraints throughout.
+
+        ``moved`` of a round is the sum over the bins of ``|fg_hist - previous fg_hist|``: every voxel that changes side moves one
+        count of one bin, so it is a lower bound on the voxels that changed side, and it is 0 exactly when the term is already fitted
+        to the histograms of its own cut -- the fixed point (the bg histograms carry the same number: per bin fg + bg is the image's
+        histogram).  The loop stops, ``converged`` True, at ``moved <= stop_below``; the first refit is always done.  ``lam`` /
+        ``eps`` of None: those the graph was built with; the values used are remembered, as by ``refit_regional_histogram``.
+
+        Returns a dict: ``rounds`` -- one dict per refit with ``fg_voxels``, ``bg_voxels`` (of the cut the refit was fitted to),
+        ``moved`` (None in the first) and ``flow`` (of the solve behind it) --, ``converged``, and ``fg_hist`` / ``bg_hist`` of the
+        final cut."""
+        self._refuse_host_merged("iterate_regional_histogram")
+        if self._binning is None or self._hist_params is None:
+            raise ValueError("iterate_regional_histogram: the graph was built without a histogram term (energy_voxel.regional_histogram)")
+        if isinstance(max_refits, bool) or not isinstance(max_refits, (int, numpy.integer)) or max_refits < 0:
+            raise ValueError("iterate_regional_histogram: max_refits = %r: a whole number >= 0" % (max_refits,))
+        if isinstance(stop_below, bool) or not isinstance(stop_below, (int, numpy.integer)) or stop_below < 0:
+            raise ValueError("iterate_regional_histogram: stop_below = %r: a whole number >= 0" % (stop_below,))
+        lam = self._hist_params[0] if lam is None else lam
+        eps = self._hist_params[1] if eps is None else eps
+        histogram_tables(numpy.zeros(1), numpy.zeros(1), lam, eps)   # (ValueError for lam / eps out of range before anything runs)
+        rounds, converged, prev = [], False, None
+        for r in range(int(max_refits) + 1):
+            fg_hist, bg_hist = self.label_histograms()
+            moved = None if prev is None else int(numpy.abs(fg_hist - prev).sum())
+            if moved is not None and moved <= stop_below:
+                converged = True
+                break
+            if r == max_refits:
+                break
+            source_table, sink_table = histogram_tables(fg_hist, bg_hist, lam, eps)
+            self.update_tweights_binned(source_table, sink_table)
+            self._hist_params = (lam, eps)
+            flow = self.maxflow()
+            rounds.append({"fg_voxels": int(fg_hist.sum()), "bg_voxels": int(bg_hist.sum()), "moved": moved, "flow": flow})
+            prev = fg_hist
+        return {"rounds": rounds, "converged": converged, "fg_hist": fg_hist, "bg_hist": bg_hist}
+
     def _add_nweights(self, offset, there, back=None):
         """mgc_add_nweights: ``there[p]`` is added to the arc p -> p + offset, ``back[p]`` (None: ``there[p]``) to the arc
         p + offset -> p; arrays of the volume's shape.  float32 / float64 go up as they are, anything else as float64."""
