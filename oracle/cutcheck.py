@@ -89,7 +89,21 @@ def lattice_edges(shape, weights):
     return np.concatenate(ii), np.concatenate(jj), np.concatenate(ww)
 
 
-TIGHT_TOL = 64 * 2.220446049250313e-16  # 64 ulp of the local capacity: what a handful of additions can lose
+def offset_edges(shape, weights):
+    """(i, j, w) of a lattice with any neighbourhood from the {offset: array} dict of
+    oracle/energy_numpy.py:boundary_weights_offsets (array[p]: the weight of the pair (p, p + offset), NaN where there is none)"""
+    shape = tuple(int(x) for x in shape)
+    strides = [int(np.prod(shape[k + 1:])) for k in range(len(shape))]
+    ids = np.arange(int(np.prod(shape)), dtype=np.int64).reshape(shape)
+    ii, jj, ww = [], [], []
+    for o, w in weights.items():
+        w = np.asarray(w, dtype=np.float64)
+        m = ~np.isnan(w)
+        ii.append(ids[m]); jj.append(ids[m] + sum(k * s for k, s in zip(o, strides))); ww.append(w[m])
+    return np.concatenate(ii), np.concatenate(jj), np.concatenate(ww)
+
+
+TIGHT_TOL = 64 *2.220446049250313e-16  # 64 ulp of the local capacity: what a handful of additions can lose
 
 
 def _record(entry):

@@ -8,12 +8,14 @@ from oracle import pipeline
 pytestmark = pytest.mark.gpu
 
 
-def _cut(image, fg, bg, term="difference_exponential", sigma=5.0):
+def _cut(image, fg, bg, term="difference_exponential", sigma=5.0, connectivity=None):
+    """``connectivity``: None = 2 * ndim; 3 ** ndim - 1 from tests/test_gpu_edge_cases_full_nb.py, which runs these inputs again"""
     from medpy_amd import graphcut
     args = (image, False) if term.endswith("linear") else (image, sigma, False)
-    g = graphcut.graph_from_voxels(fg, bg, boundary_term=getattr(graphcut.energy_voxel, "boundary_" + term), boundary_term_args=args)
+    g = graphcut.graph_from_voxels(fg, bg, boundary_term=getattr(graphcut.energy_voxel, "boundary_" + term), boundary_term_args=args,
+                                   connectivity=connectivity)
     flow = g.maxflow()
-    ref = pipeline.graphcut_voxel(fg, bg, term=term, image=image, sigma=sigma)
+    ref = pipeline.graphcut_voxel(fg, bg, term=term, image=image, sigma=sigma, connectivity=connectivity)
     np.testing.assert_array_equal(g.labels(), ref.labels)
     assert flow == pytest.approx(ref.flow, rel=1e-9, abs=1e-300)
     return g, flow
@@ -21,46 +23,66 @@ def _cut(image, fg, bg, term="difference_exponential", sigma=5.0):
 
 @pytest.mark.parametrize("shape", [(1,), (7,), (1, 1), (1, 9), (9, 1), (3, 1, 5), (1, 1, 1), (1, 1, 17), (2, 2, 2), (8, 8, 8), (9, 8, 7)])
 def test_small_and_singleton_shapes(shape):
+    _small_shape(shape)
+
+
+def _small_shape(shape, connectivity=None):
     rng = np.random.default_rng(sum(shape))
     image = rng.normal(0, 10, shape).astype(np.float32)
     fg = np.zeros(shape, bool); bg = np.zeros(shape, bool)
     fg.flat[0] = True
     if fg.size > 1:
         bg.flat[-1] = True
-    _cut(image, fg, bg)
+    return _cut(image, fg, bg, connectivity=connectivity)
 
 
 def test_no_markers_at_all():
     """reference generate.py:169-172 skips empty marker sets; with no terminals every node is free -> label 1"""
+    _no_markers()
+
+
+def _no_markers(connectivity=None):
     image = np.random.default_rng(0).normal(0, 10, (6, 7, 8)).astype(np.float32)
     z = np.zeros(image.shape, bool)
-    g, flow = _cut(image, z, z)
+    g, flow = _cut(image, z, z, connectivity=connectivity)
     assert g.labels().all() and flow == 0.0
 
 
 def test_only_foreground_or_only_background():
+    _one_sided_markers()
+
+
+def _one_sided_markers(connectivity=None):
     image = np.random.default_rng(1).normal(0, 10, (10, 9, 12)).astype(np.float32)
     z = np.zeros(image.shape, bool)
     m = np.zeros(image.shape, bool); m[2:4, 3:5, 1:6] = True
-    g, _ = _cut(image, m, z)
+    g, _ = _cut(image, m, z, connectivity=connectivity)
     assert g.labels().all()          # no sink: nobody can reach it
-    g, _ = _cut(image, z, m)
+    g, _ = _cut(image, z, m, connectivity=connectivity)
     assert not g.labels().any()      # no source: everything connected to the sink markers is sink side
 
 
 def test_everything_marked():
+    _everything_marked()
+
+
+def _everything_marked(connectivity=None):
     image = np.random.default_rng(2).normal(0, 10, (5, 6, 7)).astype(np.float32)
     fg = np.ones(image.shape, bool); bg = np.zeros(image.shape, bool)
-    _cut(image, fg, bg)
-    _cut(image, bg, fg)
-    _cut(image, fg, fg)  # every voxel both: all t-links cancel (graph.h:416-425)
+    _cut(image, fg, bg, connectivity=connectivity)
+    _cut(image, bg, fg, connectivity=connectivity)
+    _cut(image, fg, fg, connectivity=connectivity)  # every voxel both: all t-links cancel (graph.h:416-425)
 
 
 def test_repeated_solve_and_rebuild_are_idempotent():
+    _solve_again_and_rebuild()
+
+
+def _solve_again_and_rebuild(connectivity=None):
     from medpy_amd import graphcut, synthetic
     s = synthetic.sphere((24, 24, 24))
     g = graphcut.graph_from_voxels(s["fg"], s["bg"], boundary_term=graphcut.energy_voxel.boundary_difference_exponential,
-                                   boundary_term_args=(s["image"], s["sigma"], False))
+                                   boundary_term_args=(s["image"], s["sigma"], False), connectivity=connectivity)
     f1 = g.maxflow(); l1 = g.labels().copy()
     f2 = g.maxflow()
     assert f1 == f2
@@ -72,27 +94,36 @@ def test_repeated_solve_and_rebuild_are_idempotent():
 
 def test_constant_image_and_huge_dynamic_range():
     """all weights equal (exp(0) = 1) -> massive ties with exact arithmetic; and weights spanning DBL_MIN..1"""
+    _constant_and_huge_range()
+
+
+def _constant_and_huge_range(connectivity=None):
     shape = (12, 12, 12)
     fg = np.zeros(shape, bool); fg[5:7, 5:7, 5:7] = True
     bg = np.zeros(shape, bool); bg[0] = True
-    _cut(np.zeros(shape, np.float32), fg, bg)
+    _cut(np.zeros(shape, np.float32), fg, bg, connectivity=connectivity)
     image = np.zeros(shape, np.float64); image[:, :, 6:] = 1e6  # exp(-1e12/..) underflows -> DBL_MIN clamp (energy_voxel.py:299)
-    _cut(image, fg, bg, sigma=1.0)
+    _cut(image, fg, bg, sigma=1.0, connectivity=connectivity)
 
 
 def test_repeated_explicit_edges_sum_in_call_order():
     """Graph::sum_edge (graph.h:457-480) adds an edge given several times in call order; three or more contributions with
     non-associative values tell an ordered sum from any other (an atomicAdd per contribution is not ordered)."""
-    from medpy_amd import graphcut
-    from oracle import bk
     shape = (3, 4, 5)
     n = int(np.prod(shape))
     rng = np.random.default_rng(5)
-    # 40 edges, each repeated 3..6 times with values spread over 16 orders of magnitude, in shuffled call order and both orientations
     base_i = rng.integers(0, n - 1, 40)
     base_j = base_i + 1
     keep = (base_j % shape[2]) != 0  # x-neighbours inside a row
-    base_i, base_j = base_i[keep], base_j[keep]
+    _repeated_edges(shape, base_i[keep], base_j[keep], rng)
+
+
+def _repeated_edges(shape, base_i, base_j, rng, connectivity=None):
+    """every pair (base_i[k], base_j[k]) repeated 3..6 times with values spread over 16 orders of magnitude, in shuffled call order and both
+    orientations: get_edge bit-identical to BK's ordered sums in both directions, flow to 1e-12, labels equal"""
+    from medpy_amd import graphcut
+    from oracle import bk
+    n = int(np.prod(shape))
     ei, ej, cw, cr = [], [], [], []
     for a, b in zip(base_i, base_j):
         for _ in range(int(rng.integers(3, 7))):
@@ -101,7 +132,7 @@ def test_repeated_explicit_edges_sum_in_call_order():
             cw.append(float(10.0 ** rng.uniform(-8, 8))); cr.append(float(10.0 ** rng.uniform(-8, 8)))
     order = rng.permutation(len(ei))
     ei, ej, cw, cr = (np.asarray(v)[order] for v in (ei, ej, cw, cr))
-    g = graphcut.GCGraph(n, len(ei), shape=shape)
+    g = graphcut.GCGraph(n, len(ei), shape=shape, connectivity=connectivity)
     for a, b, w, r in zip(ei, ej, cw, cr):
         g.set_nweight(int(a), int(b), float(w), float(r))
     g.set_tweight(0, 5.0, 0.0); g.set_tweight(n - 1, 0.0, 5.0)
@@ -119,23 +150,32 @@ def test_repeated_explicit_edges_sum_in_call_order():
 def test_explicit_edge_batches_of_growing_size_and_rebuild():
     """the C ABI accepts a new batch after every build, of any size (the device buffers grow), and a rebuild applies the
     stored batch again"""
+    _edge_batches(None, (0, 0, 1), far=5)
+
+
+def _edge_batches(connectivity, offset, far):
+    """on a (4, 4, 4) lattice: one edge (0, 0 + offset), a build, then every pair along ``offset``, a build, a rebuild; (0, far) is refused"""
     from medpy_amd.graphcut.graph import VoxelGraph
     shape = (4, 4, 4)
-    g = VoxelGraph(shape)
+    g = VoxelGraph(shape, connectivity=connectivity)
     tr = np.zeros(64); tr[0], tr[63] = 3.0, -3.0
     g._set_tweights_merged(tr, 0.0)
-    g._add_edges([0], [1], [1.0], [1.0])
+    ids = np.arange(64, dtype=np.int64).reshape(shape)
+    i = ids[tuple(slice(0, 4 - k) for k in offset)].ravel()
+    j = i + int(ids[offset])
+    assert i[0] == 0
+    g._add_edges([0], [int(j[0])], [1.0], [1.0])
     g._build()
-    assert g.get_edge(0, 1) == 1.0
-    i = np.arange(0, 63, dtype=np.int64); i = i[(i + 1) % 4 != 0]
-    g._add_edges(i, i + 1, np.full(i.size, 2.0), np.full(i.size, 0.5))  # 48 edges after a batch of one
+    assert g.get_edge(0, int(j[0])) == 1.0
+    g._add_edges(i, j, np.full(i.size, 2.0), np.full(i.size, 0.5))  # a batch of many after a batch of one
     g._build()
-    assert g.get_edge(0, 1) == 2.0 and g.get_edge(1, 0) == 0.5 and g.get_edge(61, 62) == 2.0
-    g._build()  # rebuild without re-adding: same capacities
-    assert g.get_edge(0, 1) == 2.0 and g.get_edge(62, 61) == 0.5
+    for _ in range(2):
+        for a, b in zip(i.tolist(), j.tolist()):
+            assert g.get_edge(a, b) == 2.0 and g.get_edge(b, a) == 0.5
+        g._build()  # rebuild without re-adding: same capacities
     from medpy_amd._lib import MedpyHipError
     with pytest.raises(MedpyHipError):
-        g._add_edges([0], [5], [1.0], [1.0])  # not lattice neighbours: refused when added, naming the edge
+        g._add_edges([0], [far], [1.0], [1.0])  # not lattice neighbours: refused when added, naming the edge
 
 
 def test_plugin_edge_between_distant_voxels_goes_to_the_sparse_solver():

@@ -5,6 +5,7 @@ the terms made of IEEE basic operations), flow relative 1e-9."""
 import numpy as np
 import pytest
 
+import full_nb_cases as fc
 from oracle import energy_numpy, pipeline
 
 pytestmark = pytest.mark.gpu
@@ -23,7 +24,9 @@ def _run(s, conn, term=None, sigma=None, spacing=False, prob=None, alpha=None):
     return g, flow
 
 
-def _check(s, conn, term=None, sigma=None, spacing=False, prob=None, alpha=None, exact_energy=False):
+def _check(s, conn, term=None, sigma=None, spacing=False, prob=None, alpha=None, exact_energy=False, ties=False):
+    """``ties``: a tie-degenerate case whose cut is not the seed's surface -- labels identical, or every differing voxel in the
+    reference's ambiguity set at equal capacity in exact rationals (full_nb_cases.assert_cut)"""
     term = term or s["term"]
     sigma = s["sigma"] if sigma is None else sigma
     g, flow = _run(s, conn, term, sigma, spacing, prob, alpha)
@@ -47,8 +50,13 @@ def _check(s, conn, term=None, sigma=None, spacing=False, prob=None, alpha=None,
     kw = dict(prob=prob, alpha=alpha) if prob is not None else {}
     ref = pipeline.graphcut_voxel(s["fg"], s["bg"], term=term, image=s["image"], sigma=sigma, spacing=spacing, connectivity=conn, **kw)
     inj = pipeline.graphcut_voxel(s["fg"], s["bg"], weights=wdev, connectivity=conn, **kw)
-    np.testing.assert_array_equal(g.labels(), inj.labels)
-    np.testing.assert_array_equal(g.labels(), ref.labels)
+    if ties:
+        case = dict(shape=s["image"].shape, term=term, image=s["image"], fg=s["fg"], bg=s["bg"], prob=prob, alpha=alpha)
+        fc.assert_cut(g.labels(), flow, case, inj, wdev, "vs BK on the device's weights")
+        fc.assert_cut(g.labels(), flow, case, ref, wref, "vs oracle")
+    else:
+        np.testing.assert_array_equal(g.labels(), inj.labels)
+        np.testing.assert_array_equal(g.labels(), ref.labels)
     assert flow == pytest.approx(ref.flow, rel=1e-9)
     print("conn %d %s %s: flow %.12g, fg %.4f, %s" % (conn, term, s["image"].shape, flow, g.labels().mean(), g.stats()))
     return g
@@ -73,6 +81,13 @@ def test_26_spacing_and_exact_terms():
     s = synthetic.sphere((24, 28, 20))
     _check(s, 26, term="difference_division", sigma=3.0, spacing=(1.0, 2.0, 0.5), exact_energy=True)
     _check(s, 26, term="maximum_linear", exact_energy=True)
+    # the minimum cut of the sphere under maximum_linear is the surface of the seed: its labels come out right if no flow moves at
+    # all.  The wall (tests/full_nb_cases.py) is cut half a volume away from either marker.
+    w = fc.wall((24, 9, 10))
+    s = {"image": w["float32"], "fg": w["fg"], "bg": w["bg"], "sigma": None, "term": "maximum_linear"}
+    g = _check(s, 26, exact_energy=True, ties=True)
+    free = ~(s["fg"] | s["bg"])
+    assert 0.10 <= g.labels()[free].mean() <= 0.90
 
 
 def test_config3_26conn_plus_regional():
