@@ -259,7 +259,8 @@ int mgc_validate(mgc_handle h, mgc_validation* out);
  * |max - min| in the image's dtype).  A single handle measures it itself.  A SLAB only holds its own planes, so the
  * caller reduces the local triples {min, max, max|.|} over the ranks (min, max, max) and hands the global one back
  * before mgc_build; building a *_linear slab without it fails with MGC_ERR_STATE.  NULL forgets a range set earlier;
- * mgc_set_boundary does so too. */
+ * mgc_set_boundary does so too.  max|.| is numpy.abs(image).max() in the image's own dtype: the minimum of a signed
+ * integer type wraps onto itself there and counts with its negative value. */
 int mgc_get_image_range(mgc_handle h, double* out3);
 int mgc_set_image_range(mgc_handle h, const double* in3);
 

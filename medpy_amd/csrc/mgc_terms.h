@@ -16,18 +16,21 @@
 
 #define MGC_DBL_MIN 2.2250738585072014e-308 /* sys.float_info.min, energy_voxel.py:113,...,513 */
 
+/* one element of an image as a double; `take_abs`: of numpy.abs(image), which NumPy takes in the image's OWN dtype (energy_voxel.py:99,
+ * 558) -- a signed integer is negated at its own width, so the type's minimum wraps onto itself and stays negative:
+ * numpy.abs(int16 [-32768, 5, -7]) is [-32768, 5, 7].  The negation runs on the unsigned twin, where wrapping is defined. */
 __device__ __forceinline__ double mgc_load_as_double(const void* p, int dtype, int64_t i, bool take_abs)
 {
     double v;
     switch (dtype) {
     case MGC_U8: v = (double)((const uint8_t*)p)[i]; break;
-    case MGC_I8: { int x = ((const int8_t*)p)[i]; v = (double)(take_abs && x < 0 ? -x : x); take_abs = false; } break;
+    case MGC_I8: { int8_t x = ((const int8_t*)p)[i]; if (take_abs && x < 0) x = (int8_t)(uint8_t)(0u - (uint8_t)x); v = (double)x; take_abs = false; } break;
     case MGC_U16: v = (double)((const uint16_t*)p)[i]; break;
-    case MGC_I16: { int x = ((const int16_t*)p)[i]; v = (double)(take_abs && x < 0 ? -x : x); take_abs = false; } break;
+    case MGC_I16: { int16_t x = ((const int16_t*)p)[i]; if (take_abs && x < 0) x = (int16_t)(uint16_t)(0u - (uint16_t)x); v = (double)x; take_abs = false; } break;
     case MGC_U32: v = (double)((const uint32_t*)p)[i]; break;
-    case MGC_I32: { int64_t x = ((const int32_t*)p)[i]; v = (double)(take_abs && x < 0 ? -x : x); take_abs = false; } break;
+    case MGC_I32: { int32_t x = ((const int32_t*)p)[i]; if (take_abs && x < 0) x = (int32_t)(0u - (uint32_t)x); v = (double)x; take_abs = false; } break;
     case MGC_U64: v = (double)((const uint64_t*)p)[i]; break;
-    case MGC_I64: { int64_t x = ((const int64_t*)p)[i]; v = (double)(take_abs && x < 0 ? -x : x); take_abs = false; } break;
+    case MGC_I64: { int64_t x = ((const int64_t*)p)[i]; if (take_abs && x < 0) x = (int64_t)(0ull - (uint64_t)x); v = (double)x; take_abs = false; } break;
     case MGC_F32: v = (double)((const float*)p)[i]; break;
     default: v = ((const double*)p)[i]; break;
     }
@@ -99,16 +102,18 @@ static double mgc_range_in_dtype(double mn, double mx, int dtype)
 }
 
 
-/* min / max / max|.| of the image, one partial triple per block (deterministic), finished on the host */
+/* min / max / max of numpy.abs(image) -- in the image's dtype, see mgc_load_as_double: float(numpy.abs(image).max()) is the divisor of
+ * maximum_linear (energy_voxel.py:101) -- one partial triple per block (deterministic), finished on the host.  The third starts
+ * from -inf, not 0: an image that holds nothing but a signed type's minimum has a negative one. */
 static __global__ __launch_bounds__(256) void k_minmax(const void* image, int dtype, int64_t n, double* part)
 {
     __shared__ double smin[256], smax[256], sabs[256];
-    double mn = INFINITY, mx = -INFINITY, ma = 0.0;
+    double mn = INFINITY, mx = -INFINITY, ma = -INFINITY;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const double v = mgc_load_as_double(image, dtype, i, false);
         mn = fmin(mn, v);
         mx = fmax(mx, v);
-        ma = fmax(ma, fabs(v));
+        ma = fmax(ma, mgc_load_as_double(image, dtype, i, true));
     }
     smin[threadIdx.x] = mn; smax[threadIdx.x] = mx; sabs[threadIdx.x] = ma;
     __syncthreads();
@@ -139,7 +144,7 @@ static inline hipError_t mgc_image_range(const void* image, int dtype, int64_t n
     if (!hp) return hipErrorOutOfMemory;
     e = hipMemcpyAsync(hp, scratch, nb * 3 * sizeof(double), hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    double mn = INFINITY, mx = -INFINITY, ma = 0.0;
+    double mn = INFINITY, mx = -INFINITY, ma = -INFINITY;
     for (int b = 0; b < nb; ++b) { mn = fmin(mn, hp[3 * b]); mx = fmax(mx, hp[3 * b + 1]); ma = fmax(ma, hp[3 * b + 2]); }
     free(hp);
     *mn_out = mn; *mx_out = mx; *ma_out = ma;
