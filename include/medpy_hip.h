@@ -630,6 +630,33 @@ int msg_get_counts(msg_handle h, int64_t* nodes, int64_t* edges_added, int64_t* 
 /* every distinct arc of the graph as built (tail, head, capacity), sorted by (tail, head): bulk counterpart of get_edge,
  * used by the DIMACS writer (reference medpy/graphcut/write.py:29-76); arrays hold msg_get_counts(..., &arcs) entries */
 int msg_get_arcs(msg_handle h, int32_t* tail, int32_t* head, double* cap);
+/* The other side of the answer on a sparse graph: what mgc_cut_sets / mgc_cut_sets_tol compute for a voxel graph, over the
+ * CSR arcs.  msg_labels reports R_t, the nodes that can reach the sink in the residual graph of the maximum flow (out = 0).
+ * msg_cut_sets computes R_s = the nodes the source can reach there -- the source side of the SMALLEST minimum cut -- and the AMBIGUITY SET
+ * V \ (R_s u R_t): the nodes some minimum cut puts on the source side and another on the sink side; the cut is unique iff that set is
+ * empty.  An arc is open iff its residual capacity is > 0, no tolerance: exact where the arithmetic is exact (whole-number capacities).
+ *   msg_cut_sets_tol judges every residual against the size of the numbers it came from.  With pair(a) = the capacities as built of arc a
+ * and of its reverse arc added up, and scale(v) = the largest pair(a) over the arcs of v (0 without arcs), an arc u -> v is open iff
+ * rcap > 0 and rcap > tol * max(scale(u), scale(v)); v is a source seed iff its excess is > 0 and > tol * max(|merged t-link|, scale(v)),
+ * a sink seed iff its residual sink link is.  from_source = what the source seeds reach along open arcs, to_sink = what reaches a sink
+ * seed along them (a backward flood of its own: the labels are not consulted), ambiguous = neither.  tol = 0 gives the sets of
+ * msg_cut_sets and the complement of msg_labels; 64 * 2^-52 is the granularity the project's parity statement uses.
+ *   Output: 0 / 1, one byte per node; any pointer may be NULL (all: only the counts are computed, nothing node-sized comes down).
+ *   Valid on a handle whose last msg_maxflow converged, with no edges added and no msg_update_tweights / msg_set_tweights_merged since
+ * (cold and warm solves alike).  MGC_ERR_STATE in any other state; MGC_ERR_INVALID for a NULL handle and for tol < 0, tol >= 1 or
+ * NaN; all before anything is written.  A call leaves labels, the label snapshot of msg_labels_delta, the residual arrays, the flow,
+ * msg_get_stats and msg_get_warm_info as they were; its planes are temporary and gone when it returns.
+ *   msg_get_cut_sets_info, of the last call of either (MGC_ERR_STATE before the first): out16 = {nodes from_source, to_sink, ambiguous;
+ * passes, seeds of the forward flood; passes, seeds of the backward flood; arcs with rcap > 0 that the threshold closed; t-links (excess
+ * > 0 or sink link > 0) that it closed; 1 if the tol path ran; 0 ...}; out4 = {tol (-1 for the plain call), source_cut = capacity of
+ * the cut around from_source, sink_cut = capacity of the cut around the complement of to_sink (the plain call: the flow msg_maxflow
+ * returned), the largest scale(v) (0 for the plain call)}; the flow constant is included in both cuts, which equal the flow bit for bit
+ * where the arithmetic is exact, else up to the order of summation.  Either pointer may be NULL.  After a call of msg_cut_sets /
+ * msg_cut_sets_tol that went through, msg_last_error holds a note of where its device time went (device_ms, scale_ms, open_ms,
+ * forward_ms, backward_ms, readout_ms). */
+int msg_cut_sets(msg_handle h, uint8_t* from_source, uint8_t* ambiguous);
+int msg_cut_sets_tol(msg_handle h, double tol, uint8_t* from_source, uint8_t* to_sink, uint8_t* ambiguous);
+int msg_get_cut_sets_info(msg_handle h, int64_t* out16, double* out4);
 int msg_get_stats(msg_handle h, msg_stats* out);
 
 #ifdef __cplusplus

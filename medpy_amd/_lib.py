@@ -213,6 +213,9 @@ SIGNATURES = {
     "msg_get_counts": (_INT, [_VP, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64)]),
     "msg_get_arcs": (_INT, [_VP, _VP, _VP, _VP]),
     "msg_get_stats": (_INT, [_VP, C.POINTER(SparseStats)]),
+    "msg_cut_sets": (_INT, [_VP, _VP, _VP]),
+    "msg_cut_sets_tol": (_INT, [_VP, _DBL, _VP, _VP, _VP]),
+    "msg_get_cut_sets_info": (_INT, [_VP, _VP, _VP]),
 }
 
 _lib = None

@@ -6,6 +6,7 @@ meaning and ``ValueError`` contract -- but instead of inserting one edge per Pyt
 a CPU adjacency list, the facade records what the energy terms ask for and hands whole
 arrays to the HIP library, which builds the residual lattice in HBM and solves it there.
 """
+import collections
 import ctypes as C
 import enum
 
@@ -16,6 +17,7 @@ from . import histogram as _histogram
 from .histogram import histogram_binning, histogram_bins, histogram_tables   # noqa: F401  (the definition of the histogram regional term)
 
 
+CutSets = collections.namedtuple("CutSets", ("from_source", "to_sink", "ambiguous", "info"))   # what ``cut_sets()`` of every graph kind returns
 ULP64 = 64 * 2.0 ** -52   # the rounding granularity of the project's parity statement, for the ``tol`` of VoxelGraph.source_side & co.
 
 
@@ -952,6 +954,15 @@ class VoxelGraph(object):
         """is the minimum cut unique, i.e. the ambiguity set empty?  Counted on the device, no volume is read back."""
         return (self._cut_sets("info") if tol is None else self._cut_sets_tol(tol, "info"))["ambiguous"] == 0
 
+    def cut_sets(self, tol=None):
+        """``CutSets(from_source, to_sink, ambiguous, info)``: ``source_side(tol)``, ``sink_side(tol)``, ``ambiguous(tol)`` and
+        ``cut_sets_info(tol)`` under the one name every graph kind has (``SparseGraph.cut_sets``); arrays in the volume's shape."""
+        return CutSets(self.source_side(tol), self.sink_side(tol), self.ambiguous(tol), self.cut_sets_info(tol))
+
+    def cut_sets_unique(self, tol=None):
+        """``cut_is_unique(tol)`` under the name every graph kind has"""
+        return self.cut_is_unique(tol)
+
     def what_segment(self, i):
         """Graph::what_segment, reference graph.h:561-571."""
         seg = C.c_int(0)
@@ -1130,7 +1141,8 @@ class SparseGraph(object):
     def _no_cut_sets(self, what):
         raise NotImplementedError("medpy_amd: %s is implemented for the voxel lattice solver (1-D..3-D volumes, VoxelGraph) only; this "
                                   "graph went to the sparse-graph solver, which keeps its residual graph as CSR arcs: the forward "
-                                  "flood over tile masks does not apply (labels() is the sink side's complement)" % what)
+                                  "flood over tile masks does not apply (labels() is the sink side's complement); use cut_sets() / cut_sets_unique(), "
+                                  "which every graph kind has" % what)
 
     def source_side(self, tol=None):
         """The source side of the smallest minimum cut exists for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
@@ -1151,6 +1163,98 @@ class SparseGraph(object):
     def cut_sets_info(self, tol=None):
         """The ambiguity set exists for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
         self._no_cut_sets("cut_sets_info")
+
+    # -- the other minimum cuts (DESIGN 13c)
+    CUT_SETS_INFO_KEYS = ("from_source", "to_sink", "ambiguous", "forward_passes", "forward_seeds", "backward_passes", "backward_seeds",
+                          "arcs_closed", "tlinks_closed", "tol_path")
+
+    @property
+    def _labels(self):
+        return self.__dict__.get("_labels_cache")
+
+    @_labels.setter
+    def _labels(self, value):
+        # every edge, t-link and solve drops the cached labels by assigning None: what cut_sets() computed goes with them
+        self.__dict__["_labels_cache"] = value
+        if value is None:
+            self.__dict__["_cut_sets_cache"] = {}
+
+    def _host_arcs_unsent(self):
+        """GraphFloat / GraphInt: does a node pair carry capacities the device has not been told (what ``_send_host_arcs`` would send)"""
+        for k, a in self.__dict__.get("_host_arcs", {}).items():
+            if k[0] < k[1]:
+                b = self._host_arcs[(k[1], k[0])]
+                if (float(a[0]) + float(a[1]), float(b[0]) + float(b[1])) != self._host_sent.get(k, (0.0, 0.0)):
+                    return True
+        return False
+
+    def _refuse_unsolved_edits(self, what):
+        """the sets are those of the cut ``maxflow()`` last returned: nothing is flushed from here"""
+        d = self.__dict__
+        tr, sent = d.get("_tr"), d.get("_sent_tr")
+        if d.get("_pending", ([],))[0]:
+            held = "edges added since the last maxflow()"
+        elif self._host_arcs_unsent():
+            held = "arcs added since the last maxflow()"
+        elif tr is not None and (sent is None or sent.shape != tr.shape or not numpy.array_equal(sent, tr)):
+            held = "t-links changed since the last maxflow()"
+        elif d.get("_dev_updated"):
+            held = "t-link updates the device has not solved"
+        else:
+            return
+        raise _lib.MedpyHipError(_lib.ERR_STATE, "%s: the graph holds %s; call maxflow() first" % (what, held))
+
+    def _cut_sets_call(self, tol, planes):
+        """ONE msg_cut_sets / msg_cut_sets_tol and its info; ``planes``: three uint8 arrays or Nones (from_source, to_sink, ambiguous)"""
+        p = [None if a is None else _lib.ptr(a) for a in planes]
+        if tol is None:
+            self._call("msg_cut_sets", p[0], p[2])
+        else:
+            self._call("msg_cut_sets_tol", tol, *p)
+        out, vals = numpy.zeros(16, dtype=numpy.int64), numpy.zeros(4, dtype=numpy.float64)
+        self._call("msg_get_cut_sets_info", _lib.ptr(out), _lib.ptr(vals))
+        info = dict(zip(self.CUT_SETS_INFO_KEYS, out.tolist()), tol=None if tol is None else float(vals[0]), source_cut=float(vals[1]),
+                    sink_cut=float(vals[2]), scale_max=float(vals[3]))
+        info["tol_path"] = bool(info["tol_path"])
+        return info
+
+    def cut_sets(self, tol=None):
+        """``CutSets(from_source, to_sink, ambiguous, info)`` of the cut ``maxflow()`` last returned: bool arrays of one entry per node
+        and a dict.  ``from_source``: the nodes the source reaches in the residual graph of the maximum flow, the source side of the
+        SMALLEST minimum cut (``labels()`` is that of the largest); ``to_sink``: the nodes that reach the sink; ``ambiguous``: neither --
+        some minimum cut has them on the source side, another on the sink side.  ``tol`` None: an arc is open iff its residual is > 0
+        (msg_cut_sets; ``to_sink`` is ``~labels()``); a number in [0, 1), e.g. ``ULP64``: iff it also exceeds ``tol`` times the largest
+        capacity of an arc pair at either end (msg_cut_sets_tol): the nodes whose side does not hinge on the rounding of the solve.
+        ``info``: the three counts, ``forward_passes`` / ``forward_seeds`` / ``backward_passes`` / ``backward_seeds`` of the floods,
+        ``arcs_closed`` and ``tlinks_closed`` by the threshold, ``tol_path``, ``tol``, ``source_cut`` and ``sink_cut`` (the capacities of
+        the cuts around ``from_source`` and ``~to_sink``, both equal to the flow up to rounding) and ``scale_max``.
+        One library call per solve and ``tol``, cached until the next edge, t-link or solve.  MedpyHipError (ERR_STATE) before
+        ``maxflow()`` and while the graph holds edges or t-links that ``maxflow()`` has not seen (nothing is sent from here)."""
+        self._refuse_unsolved_edits("cut_sets")
+        tol = None if tol is None else float(tol)
+        cache = self.__dict__.setdefault("_cut_sets_cache", {})
+        if ("sets", tol) not in cache:
+            planes = [numpy.empty(self._nodes, dtype=numpy.uint8), None if tol is None else numpy.empty(self._nodes, dtype=numpy.uint8),
+                      numpy.empty(self._nodes, dtype=numpy.uint8)]
+            info = self._cut_sets_call(tol, planes)
+            to_sink = ~self.labels() if tol is None else planes[1].view(numpy.bool_)
+            cache[("sets", tol)] = CutSets(planes[0].view(numpy.bool_), to_sink, planes[2].view(numpy.bool_), info)
+            cache[("info", tol)] = info
+        return cache[("sets", tol)]
+
+    def last_note(self):
+        """what the library noted about the last call that went through: after ``cut_sets`` / ``cut_sets_unique`` the device time of
+        the call by phase (``device_ms``, ``scale_ms``, ``open_ms``, ``forward_ms``, ``backward_ms``, ``readout_ms``)"""
+        return (_lib.load().msg_last_error(self._h) or b"").decode()
+
+    def cut_sets_unique(self, tol=None):
+        """is the minimum cut unique, i.e. the ambiguity set empty (at ``tol``)?  Counted on the device: no array comes down."""
+        self._refuse_unsolved_edits("cut_sets_unique")
+        tol = None if tol is None else float(tol)
+        cache = self.__dict__.setdefault("_cut_sets_cache", {})
+        if ("info", tol) not in cache:
+            cache[("info", tol)] = self._cut_sets_call(tol, [None, None, None])
+        return cache[("info", tol)]["ambiguous"] == 0
 
     def changed_labels(self):
         """Edits by list exist for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
@@ -1765,6 +1869,13 @@ class EmbeddedLatticeGraph(object):
         """of the lattice part (mgc_get_cut_sets_info / mgc_get_cut_sets_tol_info); the cut capacities without the isolated nodes' share
         of the flow"""
         return self._inner.cut_sets_info(tol)
+
+    def cut_sets(self, tol=None):
+        """``CutSets(from_source, to_sink, ambiguous, info)`` of the four calls above; arrays flat, as ``labels()``"""
+        return CutSets(self.source_side(tol), self.sink_side(tol), self.ambiguous(tol), self.cut_sets_info(tol))
+
+    def cut_sets_unique(self, tol=None):
+        return self.cut_is_unique(tol)
 
     def stats(self):
         return self._inner.stats()
