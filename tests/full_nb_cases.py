@@ -134,20 +134,22 @@ def merged_tlinks(fg, bg, prob=None, alpha=None):
     return tr + np.where(fg.ravel(), MAX, 0.0) - np.where(bg.ravel(), MAX, 0.0)
 
 
-def expected_weights(term, image, spacing):
-    """(forward offsets, {offset: array}) of the restatement at connectivity 3^n - 1"""
+def expected_weights(term, image, spacing, connectivity=None):
+    """(forward offsets, {offset: array}) of the restatement at connectivity 3^n - 1 (``connectivity``: at that one)"""
     image = np.asarray(image)
-    offs = energy_numpy.forward_offsets(image.ndim, full_connectivity(image.ndim))
+    offs = energy_numpy.forward_offsets(image.ndim, connectivity or full_connectivity(image.ndim))
     return offs, energy_numpy.boundary_weights_offsets(term, image, offs, sigma_of(term), spacing)
 
 
-def reference(shape, term, dtype, spacing_on, with_regional=False):
-    """the oracle's cut of a wall case, solved once per process: (case dict, pipeline.Cut)"""
-    key = ("ref", tuple(shape), term, dtype, bool(spacing_on), bool(with_regional))
+def reference(shape, term, dtype, spacing_on, with_regional=False, connectivity=None):
+    """the oracle's cut of a wall case, solved once per process: (case dict, pipeline.Cut).  At connectivity 3^n - 1, or at
+    ``connectivity``"""
+    conn = connectivity or full_connectivity(len(shape))
+    key = ("ref", tuple(shape), term, dtype, bool(spacing_on), bool(with_regional)) + ((conn,) if connectivity else ())
     if key not in _CACHE:
         w = wall(shape)
         case = {"shape": tuple(shape), "term": term, "image": w[dtype], "fg": w["fg"], "bg": w["bg"], "sigma": sigma_of(term),
-                "spacing": spacing_of(shape, spacing_on), "conn": full_connectivity(len(shape)), "prob": None, "alpha": None}
+                "spacing": spacing_of(shape, spacing_on), "conn": conn, "prob": None, "alpha": None}
         if with_regional:
             case["prob"], case["alpha"] = regional(shape, term)
         kw = dict(prob=case["prob"], alpha=case["alpha"]) if with_regional else {}
@@ -157,14 +159,19 @@ def reference(shape, term, dtype, spacing_on, with_regional=False):
     return _CACHE[key]
 
 
-def reference_regional_only(shape):
-    """MGC_TERM_NONE at the full neighbourhood: a regional map and the markers of the wall, no boundary term (no n-link at all)"""
-    key = ("ref_none", tuple(shape))
+def reference_regional_only(shape, connectivity=None):
+    """MGC_TERM_NONE at the full neighbourhood (or at ``connectivity``): a regional map and the markers of the wall, no boundary term
+    (no n-link at all)"""
+    conn = connectivity or full_connectivity(len(shape))
+    key = ("ref_none", tuple(shape)) + ((conn,) if connectivity else ())
     if key not in _CACHE:
         w = wall(shape)
         prob, alpha = regional(shape, "difference_linear")
         case = {"shape": tuple(shape), "term": None, "image": None, "fg": w["fg"], "bg": w["bg"], "sigma": None, "spacing": False,
-                "conn": full_connectivity(len(shape)), "prob": prob, "alpha": alpha}
+                "conn": conn, "prob": prob, "alpha": alpha}
+        if conn == 2 * len(shape):   # the reference's own neighbourhood: no term, no n-link
+            _CACHE[key] = (case, pipeline.graphcut_voxel(w["fg"], w["bg"], prob=prob, alpha=alpha))
+            return _CACHE[key]
         none = {o: np.full(shape, np.nan) for o in energy_numpy.forward_offsets(len(shape), case["conn"])}
         _CACHE[key] = (case, pipeline.graphcut_voxel(w["fg"], w["bg"], weights=none, connectivity=case["conn"], prob=prob, alpha=alpha))
     return _CACHE[key]
