@@ -79,6 +79,8 @@ typedef struct mgc_stats {
     int64_t discharge_wave_launches;
     int64_t discharge_wave_tiles;
     int64_t timing_stride;     /* every n-th solver launch of a kind carries a HIP event pair; the _ms are their mean x launches */
+    int64_t held_wakeups;      /* tile faces across which k_discharge_w left flow in the outbox without waking the neighbour (thin flow held back during
+                                  the early cycles of a solve that floods against walls; 0 where the rule did not engage) */
     double  update_ms;         /* device time of the last t-link update (mgc_update_*): k_update_tlinks + its flow-constant sum; 0 after mgc_build.
                                   After mgc_edit_markers: plus its scatter kernel */
     double  delta_ms;          /* device time of the last mgc_labels_delta: compare + count + scan (+ the ordered write when the ids were delivered) */

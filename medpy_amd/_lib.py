@@ -32,7 +32,7 @@ class Stats(C.Structure):
         ("relabel_tiles", C.c_int64), ("global_relabels", C.c_int64), ("phases", C.c_int64), ("ntiles", C.c_int64),
         ("nvox", C.c_int64), ("device_bytes", C.c_int64), ("reserved", C.c_int64 * 3),
         ("discharge_wave_ms", C.c_double), ("discharge_wave_launches", C.c_int64), ("discharge_wave_tiles", C.c_int64),
-        ("timing_stride", C.c_int64), ("update_ms", C.c_double), ("delta_ms", C.c_double),
+        ("timing_stride", C.c_int64), ("held_wakeups", C.c_int64), ("update_ms", C.c_double), ("delta_ms", C.c_double),
     ]
 
     def as_dict(self):

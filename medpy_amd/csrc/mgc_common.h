@@ -81,7 +81,8 @@
 #define MGC_CNT_DEFERRED 28    /* (during a solve; k_build's MGC_CNT_NOT_FULL is read before it starts) border tiles a halo pack had to leave
                                   for the next exchange because the message was full (MgcLattice::halo_max_rec) */
 #define MGC_CNT_WAVE_TILES 29  /* running total of the tiles k_discharge_w visited (count[8] pools both discharge kernels) */
-#define MGC_CNT_NOT_FULL 28    /* k_build: tiles holding an n-link inside the volume that is not residual (0: the first global relabel is a distance transform) */
+#define MGC_CNT_HELD_WAKEUPS 10 /* (6-neighbourhood) running total of the faces across which k_discharge_w left flow without waking the neighbour (MGCW_HOLD_THIN) */
+#define MGC_CNT_NOT_FULL 28   /* k_build: tiles holding an n-link inside the volume that is not residual (0: the first global relabel is a distance transform) */
 
 /* *p = v as a STREAMING store on the GPU: the write-back of a tile's own state by a discharge (excess, residual planes, masks) is not read again before the
  * caches have turned over many times; written through them it only pushes out what the visits in flight are about to read (measured in round 6:

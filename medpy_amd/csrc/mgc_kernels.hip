@@ -450,6 +450,16 @@ __device__ __forceinline__ void mgc_clear_counter(const MgcLattice& L, int c)
     if (c >= 0 && blockIdx.x == 0 && (int)threadIdx.x < L.nshard) *mgc_counter(L, c, (int)threadIdx.x) = 0;
 }
 
+#ifndef MGC_HOLD_THIN_CYCLES
+#define MGC_HOLD_THIN_CYCLES 1 /* MGCW_HOLD_THIN (mgc_wave_ops.inl) for the first n cycles of a solve that floods against walls: the flood cycle (0: off).
+                                  Measured on MI355X, ms per headline step at 2^-20 (profiles/hold_thin_ab.jsonl): off 16.83 - 16.88 (537 k visits), 1: 15.52 -
+                                  15.63 (457 k), 2: 16.05 - 16.08 (440 k: what the cycle behind the flood holds back keeps the relabel behind it from finding
+                                  the source sealed, one more cycle and relabel follow, 58 -> 74 phases; 256^3 4.13 -> 4.75 - 4.82 ms that way, 4.11 - 4.19 at 1) */
+#endif
+#ifndef MGC_HOLD_THIN_LOG2
+#define MGC_HOLD_THIN_LOG2 -10 /* ... flow of at most 2^n x the largest weight the boundary term can produce waits.  One cycle, 512^3 / 384^3: -30 16.55 / 8.99 ms,
+                                  -20 15.63 / 8.60, -10 15.56 / 8.50 (parent 16.85 / 9.01) */
+#endif
 #ifndef MGCW_DISCHARGE_WAVES
 #define MGCW_DISCHARGE_WAVES 2 /* waves per SIMD the register allocator leaves room for: 256 VGPRs each.  Rounds 2 - 5 (150 - 360 registers spilled at three):
                                   24.0 ms of discharge kernels per step at 2, 31.8 at 3, 57 at 4.  Round 6 built the kernel WITHOUT a byte of scratch at 168
@@ -462,7 +472,7 @@ __device__ __forceinline__ void mgc_clear_counter(const MgcLattice& L, int c)
 #endif
 template <int REP> /* in-plane push steps per (slot, direction) and sweep: 1, or MGCW_REPEAT_MAX (mgc_wave_ops.inl) */
 __global__ __launch_bounds__(MGCW_LANES) __attribute__((amdgpu_waves_per_eu(MGCW_DISCHARGE_WAVES, MGCW_DISCHARGE_WAVES)))
-void k_discharge_w(MgcLattice L, int lst, uint32_t phase, int sweeps, int flags, int tk, int zero_idx, int stagger)
+void k_discharge_w(MgcLattice L, int lst, uint32_t phase, int sweeps, int flags, int tk, int zero_idx, int stagger, double hold_below)
 {
     __shared__ MgcWaveShared S;
     GpuWave w(S);
@@ -492,8 +502,8 @@ void k_discharge_w(MgcLattice L, int lst, uint32_t phase, int sweeps, int flags,
         w.new_tile();
         w.mark(1); /* between two tiles */
         /* the tile id is wave-uniform: keep it (and every base address derived from it) in SGPRs */
-        if (__builtin_amdgcn_readfirstlane(st) & (int)MGC_ST_SINK) mgcw_discharge_impl<true, REP>(w, L, tile, phase, sweeps, flags | ((flags & MGCW_BFS_SINK) ? MGCW_BFS : 0));
-        else mgcw_discharge_impl<false, REP>(w, L, tile, phase, sweeps, flags);
+        if (__builtin_amdgcn_readfirstlane(st) & (int)MGC_ST_SINK) mgcw_discharge_impl<true, REP>(w, L, tile, phase, sweeps, flags | ((flags & MGCW_BFS_SINK) ? MGCW_BFS : 0), hold_below);
+        else mgcw_discharge_impl<false, REP>(w, L, tile, phase, sweeps, flags, hold_below);
 #if MGCW_RUNAHEAD
         tile = w.next_tile; /* resolved inside the visit (hint_begin / hint_end in mgcw_discharge_impl) */
         st = w.nst;
@@ -2793,6 +2803,14 @@ struct mgc_graph {
     uint16_t* d_ds16 = nullptr; /* radial labels: 1 + L1 distance from the nearest voxel that held excess when the solve began (allocated on first use) */
     int32_t* d_hexact = nullptr; /* radial labels: the exact labels of the last global relabel, kept aside while the labels in L.height are the radial ones */
     bool radial_on = false;      /* the discharges run on radial labels (every saturation marks the tile DIRTY) */
+    int cycle_no = 0;            /* cycles of colour phases of the current solve so far (HipDevT::set_radial is called once per cycle) */
+    bool first_cycle_radial = false; /* ... and the first of them ran on radial labels: the graph holds walls, and the solve floods against them */
+    /* MGCW_HOLD_THIN (mgc_wave_ops.inl): during the first hold_thin_cycles cycles of such a solve k_discharge_w wakes a neighbour only for flow
+     * above 2^hold_thin_log2 x the largest weight the boundary term can produce (1, or 1 / the smallest spacing: the convention of
+     * MGC_WALL_WEIGHT).  Compile-time defaults, MEDPY_HIP_HOLD_THIN_CYCLES / MEDPY_HIP_HOLD_THIN_LOG2 read once per handle for A/B runs.
+     * 0 cycles: off.  Measured: profiles/hold_thin_ab.jsonl */
+    int hold_thin_cycles = MGC_HOLD_THIN_CYCLES;
+    int hold_thin_log2 = MGC_HOLD_THIN_LOG2;
     int radial_cycle_no = 0;     /* radial cycles of the current solve so far: from the second on, flow taken in marks a tile DIRTY too (MGCW_INFLOW_DIRTY) */
     bool all_residual = false; /* k_build found every n-link inside the volume residual */
     int exact_sink_tiles = 1;  /* k_discharge_w: exact in-tile labels per visit for the tiles that hold a sink link (MGCW_BFS_SINK; parameter
@@ -3199,7 +3217,30 @@ struct HipDevT {
         return true;
     }
     /* ---- radial labels of the flood phase (mgc_dt_ops.inl; the schedule: mgc_driver.inl) ---- */
-    void set_radial(bool on) { h->radial_on = on; if (on) h->radial_cycle_no++; } /* (radial_cycle_no: reset by whoever starts a solve) */
+    void set_radial(bool on) /* (radial_cycle_no, cycle_no: reset by whoever starts a solve) */
+    {
+        h->radial_on = on;
+        if (on) h->radial_cycle_no++;
+        if (++h->cycle_no == 1) h->first_cycle_radial = on;
+    }
+    /* MGCW_HOLD_THIN for the launches of this cycle?  Single handles only (the slab schedule counts on border flow being announced), a solve from
+     * scratch whose first cycle ran on radial labels (the wall rule's verdict: a graph without walls lives on thin flows), capacities the
+     * boundary term determines (explicit or dense n-links and tables have no known scale), and only the first cycle(s): held flow moves one
+     * tile per global relabel, and a relabel that finds held flow in front of the wall does not find the source sealed */
+    bool hold_thin() const
+    {
+        return !FULL && h->nranks == 1 && h->hold_thin_cycles > 0 && h->first_cycle_radial && h->cycle_no <= h->hold_thin_cycles &&
+               !h->L.cap0 && !h->d_lut && h->term != MGC_TERM_NONE;
+    }
+    double hold_below() const
+    {
+        double smin = 1.0;
+        if (h->has_spacing) {
+            smin = h->spacing[2];
+            for (int k = 3 - h->ndim; k < 2; ++k) smin = h->spacing[k] < smin ? h->spacing[k] : smin;
+        }
+        return ldexp(1.0, h->hold_thin_log2) / smin;
+    }
     bool radial_begin(int c_min)
     {
         if (FULL) return false;
@@ -3343,12 +3384,13 @@ struct HipDevT {
             const bool exact_sink = h->exact_sink_tiles == 2 || (h->exact_sink_tiles == 1 && 2 * (int64_t)h->sink_tiles > h->L.ntiles);
             /* a visit that starts from exact in-tile labels needs fewer sweeps to move what it can (tie-heavy 512^3: 796 ms at 12, 731 at 8, 788 at 6) */
             if (exact_sink && h->exact_sink_tiles == 1 && sweeps > h->sink_sweeps) sweeps = h->sink_sweeps;
-            const int dflags = ((h->wave_kernels & 4) ? MGCW_BFS : 0) | (exact_sink ? MGCW_BFS_SINK : 0) | (h->radial_on ? MGCW_SAT_DIRTY : 0) | ((h->radial_on && h->radial_cycle_no > 1) ? MGCW_INFLOW_DIRTY : 0);
+            const int dflags = ((h->wave_kernels & 4) ? MGCW_BFS : 0) | (exact_sink ? MGCW_BFS_SINK : 0) | (h->radial_on ? MGCW_SAT_DIRTY : 0) | ((h->radial_on && h->radial_cycle_no > 1) ? MGCW_INFLOW_DIRTY : 0) | (hold_thin() ? MGCW_HOLD_THIN : 0);
+            const double hold = (dflags & MGCW_HOLD_THIN) ? hold_below() : 0.0;
             /* repeated in-plane steps (mgcw_discharge_impl<.., MGCW_REPEAT_MAX>): decided per SOLVE (repeat_now, mgc_maxflow / mgc_solve_slabs) */
             const bool rep = (h->repeat_now && h->est_phase_tiles >= h->repeat_min_tiles) ||
                              ((h->repeat_steps & 4) && h->radial_cycle_no > 0 && !h->radial_on && h->L.ntiles >= h->repeat_flood_min_tiles); /* (bit 2: the flood is over) */
-            if (rep) hipLaunchKernelGGL(k_discharge_w<MGCW_REPEAT_MAX>, dim3(h->wave_grid_dis), dim3(MGCW_LANES), 0, h->stream, h->L, lst, phase, sweeps, dflags, h->tk_dis, zero_idx, h->wave_stagger);
-            else hipLaunchKernelGGL(k_discharge_w<1>, dim3(h->wave_grid_dis), dim3(MGCW_LANES), 0, h->stream, h->L, lst, phase, sweeps, dflags, h->tk_dis, zero_idx, h->wave_stagger);
+            if (rep) hipLaunchKernelGGL(k_discharge_w<MGCW_REPEAT_MAX>, dim3(h->wave_grid_dis), dim3(MGCW_LANES), 0, h->stream, h->L, lst, phase, sweeps, dflags, h->tk_dis, zero_idx, h->wave_stagger, hold);
+            else hipLaunchKernelGGL(k_discharge_w<1>, dim3(h->wave_grid_dis), dim3(MGCW_LANES), 0, h->stream, h->L, lst, phase, sweeps, dflags, h->tk_dis, zero_idx, h->wave_stagger, hold);
             h->tk_dis ^= 1;
             h->launches[MGC_LAUNCH_DISCHARGE_W]++;
         }
@@ -3818,6 +3860,8 @@ static int mgc_create_impl(int ndim, const int64_t* shape, int connectivity, int
     MGC_HIP(h, hipHostGetDevicePointer((void**)&h->d_look, h->h_look, 0));
     MGC_HIP(h, hipMemsetAsync(L.count, 0, MGC_NCOUNT * (1 + MGC_NSHARD) * sizeof(int32_t), h->stream));
     MGC_HIP(h, hipStreamSynchronize(h->stream));
+    if (const char* e = getenv("MEDPY_HIP_HOLD_THIN_CYCLES")) h->hold_thin_cycles = atoi(e); /* A/B runs and tests */
+    if (const char* e = getenv("MEDPY_HIP_HOLD_THIN_LOG2")) h->hold_thin_log2 = atoi(e);
     if (const char* wv = getenv("MEDPY_HIP_WAVE")) { h->wave_kernels = atoi(wv); h->wave_set = true; } /* development aid: A/B the kernel forms */
     { /* persistent grids of the wave kernels: as many waves as the device keeps resident */
         hipDeviceProp_t prop;
@@ -4195,7 +4239,7 @@ static int mgc_solve_slabs_on(mgc_handle* hs, int n, const mgc_transport* cb, co
         x.allreduce(&walls, 1, 0);
         P.radial = walls >= h0->radial_min_walls ? 1 : 0;
     }
-    for (int i = 0; i < n; ++i) { hs[i]->repeat_now = (h0->repeat_steps & (P.radial ? 2 : 1)) != 0; hs[i]->radial_cycle_no = 0; }
+    for (int i = 0; i < n; ++i) { hs[i]->repeat_now = (h0->repeat_steps & (P.radial ? 2 : 1)) != 0; hs[i]->radial_cycle_no = 0; hs[i]->cycle_no = 0; hs[i]->first_cycle_radial = false; }
     MgcSolveStats st;
     const int rc = mgc_solve(group, h0->L, P, st, lay);
     hipError_t first = hipSuccess;
@@ -5701,6 +5745,9 @@ int mgc_maxflow(mgc_handle h, double* flow)
             if (P.radial == 2) P.radial = h->wall_tiles >= h->radial_min_walls ? 1 : 0;
             h->repeat_now = (h->repeat_steps & (P.radial ? 2 : 1)) != 0;
             h->radial_cycle_no = 0;
+            h->cycle_no = 0;
+            h->first_cycle_radial = false;
+            h->zero_mask |= 1u << MGC_CNT_HELD_WAKEUPS;
             if (h->prepush && h->d_prob && !h->rounds_set) P.rounds_per_relabel = 2; /* (a pre-pushed graph, see the 26-neighbourhood branch; 512^3 + regional map: 19.0 ms at 3, 17.8 at 2, 20.1 at 4; without the pre-push 21.4) */
             rc = mgc_solve(dev, L, P, st);
         } else {
@@ -5764,6 +5811,7 @@ int mgc_maxflow(mgc_handle h, double* flow)
         h->stats.reserved[0] = dev.readbacks;
         h->stats.reserved[1] = st.radial_cycles;
         h->stats.reserved[2] = h->wall_tiles;
+        h->stats.held_wakeups = L.ndir == 6 ? h->h_count[MGC_CNT_HELD_WAKEUPS] : 0; /* (as of the solve's last counter read-back: behind its last discharge) */
         h->stats.discharge_tiles = st.discharge_tiles;
         h->stats.discharge_wave_tiles = L.ndir == 6 ? h->h_count[MGC_CNT_WAVE_TILES] : st.discharge_tiles; /* (as of the solve's last counter read-back) */
         h->stats.relabel_tiles = st.relabel_tiles;

@@ -385,6 +385,9 @@ MGC_HD void mgc_discharge_tile(X& x, const MgcLattice& L, int tile, uint32_t pha
         const uint32_t st_now = L.status[tile];
         mgc_load_nbrs(x, L, tile, t);
         mgc_load_halo_inbox(x, L, tile, t);
+        /* (depflag is free during a discharge) face t of this tile still carries its outbox flag: flow that the wave form held back without
+         * waking the neighbour (MGCW_HOLD_THIN, mgc_wave_ops.inl) may wait there, and what this visit pushes across the face is added to it */
+        if (t < 6 && x.S.nbr[t] >= 0 && mgc_owned(L, x.S.nbr[t])) x.S.depflag[t] = (int32_t)((L.oflags[tile] >> t) & 1u);
         ob0[t] = ob1[t] = ob2[t] = 0.0;
         lostarc[t] = 0;
         if (!(st_now & MGC_ST_SINK)) snk[t] = 0.0; /* the build writes the sink plane only where a tile has a sink link */
@@ -590,10 +593,14 @@ MGC_HD void mgc_discharge_tile(X& x, const MgcLattice& L, int tile, uint32_t pha
         t_rmask[(unsigned)t] = (uint8_t)m;
         t_height[(unsigned)t] = x.S.hs[mgc_hs_index(z, y, xx)];
         /* plain stores: the neighbour emptied these slots when it last absorbed, and it always runs (or absorb_all
-         * does) between two of our discharges */
-        if (ob0[t] != 0.0) t_obox[(unsigned)((xx == 0 ? 0 : 1) * MGC_TF + mgc_face_index(0, z, y, xx))] = ob0[t];
-        if (ob1[t] != 0.0) t_obox[(unsigned)((y == 0 ? 2 : 3) * MGC_TF + mgc_face_index(1, z, y, xx))] = ob1[t];
-        if (ob2[t] != 0.0) t_obox[(unsigned)((z == 0 ? 4 : 5) * MGC_TF + mgc_face_index(2, z, y, xx))] = ob2[t];
+         * does) between two of our discharges -- unless the wave form held thin flow back (depflag, see the load) */
+        auto put = [&](int f, int k, double ob) {
+            double* slot = &t_obox[(unsigned)(f * MGC_TF + k)];
+            *slot = x.S.depflag[f] ? ob + *slot : ob;
+        };
+        if (ob0[t] != 0.0) put(xx == 0 ? 0 : 1, mgc_face_index(0, z, y, xx), ob0[t]);
+        if (ob1[t] != 0.0) put(y == 0 ? 2 : 3, mgc_face_index(1, z, y, xx), ob1[t]);
+        if (ob2[t] != 0.0) put(z == 0 ? 4 : 5, mgc_face_index(2, z, y, xx), ob2[t]);
         if (t < 6 && x.S.faceflag[t]) {
             x.atomic_or(&L.oflags[tile], 1u << t);
             mgc_enqueue(x, L, (int)((phase + 1) & 3u), L.stamp, phase + 1, x.S.nbr[t]);

@@ -70,6 +70,11 @@
                                  elsewhere labels come from far away and the stored ones are as good (weak contrast: 69 -> 80 ms with
                                  MGCW_BFS on every tile) */
 #define MGCW_INFLOW_DIRTY 8    /* ... (with MGCW_SAT_DIRTY) a radial cycle that is NOT the first of its solve: flow that comes in marks the tile DIRTY too (see the tail) */
+#define MGCW_HOLD_THIN 16      /* ... a neighbour is woken across a face only if some voxel pushed more than `hold_below` across it; thinner flow waits in the
+                                 outbox (flagged in oflags as ever) for whoever visits the neighbour next, at the latest the absorb_all of the next
+                                 global relabel.  For the early cycles of a solve that floods against walls (HipDevT::discharge): while a wall is
+                                 being closed every visit of a wall tile lets 1e-19 .. 1e-7 per voxel through, and each such trickle used to be
+                                 walked tile by tile to the faces of the volume, a full visit per tile, saturating nothing on its way */
 #define MGCW_SAT_DIRTY 4      /* ... the visit runs on RADIAL labels (mgc_dt_ops.inl): any saturated arc marks the tile DIRTY -- whether a voxel
                                  keeps "a residual arc one label down" says nothing about its distance when the labels are not distances */
 
@@ -267,7 +272,7 @@ MGC_HD void mgcw_prefetch_tile(W& w, const MgcLattice& L, int tile)
  * juggling, and a (slot, direction) pair in which nobody pushes costs three compares and a scalar branch.
  * ------------------------------------------------------------------------------------- */
 template <bool SINK, int REP = 1, class W>
-MGC_HD void mgcw_discharge_impl(W& w, const MgcLattice& L, int tile, uint32_t phase, int max_sweeps, int flags)
+MGC_HD void mgcw_discharge_impl(W& w, const MgcLattice& L, int tile, uint32_t phase, int max_sweeps, int flags, double hold_below = 0.0)
 {
     typename W::template Reg<double, 8> e;
     typename W::template Reg<double, 8> r[6];
@@ -291,6 +296,7 @@ MGC_HD void mgcw_discharge_impl(W& w, const MgcLattice& L, int tile, uint32_t ph
     w.lanes([&](int l) MGCW_INL {
         mgcw_halo_issue(w, L, tile, l, hv, dnb, ofl);
         st0(l, 0) = (int)L.status[tile];
+        if ((flags & MGCW_HOLD_THIN) && l == 6) ofl(l, 0) = (int)L.oflags[tile]; /* lane 6: this tile's own flags -- flow held back by an earlier visit may still wait in its outbox (see the tail) */
         mgcw_static_for<8>([&](auto KK) MGCW_INL {
             constexpr int K = decltype(KK)::value;
             e(l, K) = w.ld(t_excess, K * 64 + l);
@@ -595,6 +601,32 @@ MGC_HD void mgcw_discharge_impl(W& w, const MgcLattice& L, int tile, uint32_t ph
         if (w.any([&](int l) MGCW_INL -> bool { return (nz(l, 0) & 4) != 0; })) face |= 16u;
         if (w.any([&](int l) MGCW_INL -> bool { return (nz(l, 0) & 8) != 0; })) face |= 32u;
     }
+    /* MGCW_HOLD_THIN: which of those faces carry enough to be worth a visit of the neighbour (wakeface), and across which of them flow
+     * of an earlier visit still waits in the outbox because nobody was woken for it (carry: the outbox stores below are plain stores,
+     * so what waits there is added to what goes out now -- the neighbour is idle during this phase, the slots are ours) */
+    uint32_t wakeface = face, carry = 0;
+    if (flags & MGCW_HOLD_THIN) {
+        typename W::template Reg<int, 1> nz;
+        w.lanes([&](int l) MGCW_INL {
+            int m = 0;
+            mgcw_static_for<8>([&](auto KK) MGCW_INL {
+                constexpr int K = decltype(KK)::value;
+                m |= (obx(l, K) > hold_below ? 1 : 0) | (oby(l, K) > hold_below ? 2 : 0);
+            });
+            nz(l, 0) = m | (obz(l, 0) > hold_below ? 4 : 0) | (obz(l, 1) > hold_below ? 8 : 0);
+        });
+        wakeface = 0;
+        if (w.any([&](int l) MGCW_INL -> bool { return (nz(l, 0) & 1) && (l & 7) == 0; })) wakeface |= 1u;
+        if (w.any([&](int l) MGCW_INL -> bool { return (nz(l, 0) & 1) && (l & 7) == 7; })) wakeface |= 2u;
+        if (w.any([&](int l) MGCW_INL -> bool { return (nz(l, 0) & 2) && (l >> 3) == 0; })) wakeface |= 4u;
+        if (w.any([&](int l) MGCW_INL -> bool { return (nz(l, 0) & 2) && (l >> 3) == 7; })) wakeface |= 8u;
+        if (w.any([&](int l) MGCW_INL -> bool { return (nz(l, 0) & 4) != 0; })) wakeface |= 16u;
+        if (w.any([&](int l) MGCW_INL -> bool { return (nz(l, 0) & 8) != 0; })) wakeface |= 32u;
+#pragma unroll
+        for (int f = 0; f < 6; ++f)
+            if (((face >> f) & 1u) && w.any([&](int l) MGCW_INL -> bool { return l == 6 && (((uint32_t)ofl(l, 0) >> f) & 1u); })) carry |= 1u << f;
+    }
+    const int held = __builtin_popcount(face & ~wakeface); /* faces with flow whose neighbour is not woken (MGC_CNT_HELD_WAKEUPS) */
     /* lane l < 6 wakes the neighbour across face l, lane 6 this tile itself (budget exhausted with work left) */
     typename W::template Reg<int, 4> wk; /* tile to wake (-1: none), its list, claimed?, position */
     int32_t* const list_nbr = L.list[(phase + 1) & 3u];
@@ -603,7 +635,7 @@ MGC_HD void mgcw_discharge_impl(W& w, const MgcLattice& L, int tile, uint32_t ph
     w.lanes([&](int l) MGCW_INL {
         int target = -1, lst = 0;
         uint32_t ep = 0;
-        if (l < 6 && ((face >> l) & 1u)) { target = mgc_tile_nbr(L, tz, ty, tx, l); ep = phase + 1; }
+        if (l < 6 && ((wakeface >> l) & 1u)) { target = mgc_tile_nbr(L, tz, ty, tx, l); ep = phase + 1; }
         if (l == 6 && active) { target = tile; ep = phase + 2; }
         lst = (int)(ep & 3u);
         if (target >= 0 && !mgc_owned(L, target)) target = -1; /* a ghost tile is discharged by the slab that owns it */
@@ -614,6 +646,7 @@ MGC_HD void mgcw_discharge_impl(W& w, const MgcLattice& L, int tile, uint32_t ph
         /* claim: whoever finds another stamp there is the first to queue the tile for that phase.  (What comes back is only
          * looked at further down: the wait for it sits behind the votes and the staging below.) */
         if (target >= 0) wk(l, 2) = (int)w.atomic_exch(&L.stamp[target], ep);
+        if (l == 7 && held) (void)w.atomic_add(&L.count[MGC_CNT_HELD_WAKEUPS], held);
     });
     bool has_sink = false;
     /* excess under a finite label (excess under an INF label is dead for good): what the slot votes that ended the sweeps said */
@@ -670,6 +703,13 @@ MGC_HD void mgcw_discharge_impl(W& w, const MgcLattice& L, int tile, uint32_t ph
         w.S.inbox[4][l] = obz(l, 0);
         w.S.inbox[5][l] = obz(l, 1);
     });
+    if (carry) { /* (MGCW_HOLD_THIN, rare: a second visit before the neighbour came for what the first one held back) */
+        w.lanes([&](int l) MGCW_INL {
+#pragma unroll
+            for (int f = 0; f < 6; ++f)
+                if ((carry >> f) & 1u) w.S.inbox[f][l] += w.ld(t_obox + f * MGC_TF, l);
+        });
+    }
     w.mark(6); /* face votes, claims issued, tail votes, outbox staged */
     w.lanes([&](int l) MGCW_INL { /* positions in the lists (region of this workgroup, MgcLattice::scount) */
         const uint32_t ep = l == 6 ? phase + 2 : phase + 1;
@@ -732,10 +772,10 @@ MGC_HD void mgcw_discharge_impl(W& w, const MgcLattice& L, int tile, uint32_t ph
 }
 
 template <int REP = 1, class W>
-MGC_HD void mgcw_discharge_tile(W& w, const MgcLattice& L, int tile, uint32_t phase, int max_sweeps, int flags)
+MGC_HD void mgcw_discharge_tile(W& w, const MgcLattice& L, int tile, uint32_t phase, int max_sweeps, int flags, double hold_below = 0.0)
 {
-    if (L.status[tile] & MGC_ST_SINK) mgcw_discharge_impl<true, REP>(w, L, tile, phase, max_sweeps, flags | ((flags & MGCW_BFS_SINK) ? MGCW_BFS : 0));
-    else mgcw_discharge_impl<false, REP>(w, L, tile, phase, max_sweeps, flags);
+    if (L.status[tile] & MGC_ST_SINK) mgcw_discharge_impl<true, REP>(w, L, tile, phase, max_sweeps, flags | ((flags & MGCW_BFS_SINK) ? MGCW_BFS : 0), hold_below);
+    else mgcw_discharge_impl<false, REP>(w, L, tile, phase, max_sweeps, flags, hold_below);
 }
 
 /* ---------------------------------------------------------------------------------------
