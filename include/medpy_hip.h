@@ -382,6 +382,36 @@ int mgc_update_tweights_binned(mgc_handle h, int64_t nbins, double lo, double wi
  * handle.  Changes nothing on the handle: labels, label snapshot, residual graph, statistics, launch counts and device_bytes stay. */
 int mgc_label_histograms(mgc_handle h, const uint8_t* labels, int64_t nbins, double lo, double width, int64_t* fg_hist, int64_t* bg_hist, int64_t* out4);
 
+/* The connected components of a label plane on the handle's lattice, found on the device.  The plane is the labels of
+ * the current cut (labels NULL; the states of mgc_cut_sets) or one byte per voxel in C order on the host, any byte but 0 being
+ * foreground (any single handle, built or not).  side 1 takes the components of the foreground, 0 those of the background; full 0
+ * the face neighbourhood (2 / 4 / 6 neighbours), 1 the full one (2 / 8 / 26).  Neighbours outside the volume do not exist.
+ *   The components are numbered 1 .. K by their FIRST voxel, the smallest voxel id they hold: the numbering of
+ * scipy.ndimage.label.  ids (nvox entries or NULL): the number of every voxel's component, 0 on the other side.  first / size /
+ * flags (cap entries each; NULL allowed when cap is 0): row k - 1 describes component k -- first voxel, voxel count, and flag bits
+ * 1 = holds a foreground marker of the handle, 2 = holds a background marker, 4 = touches the border of the volume (some coordinate
+ * 0 or dim - 1 among the axes of extent > 1).  When K > cap the table holds the first cap components and the call still succeeds:
+ * look at K and call again.
+ *   out8 (or NULL) = {K, voxels of side, size of the largest component, its id (ties: the smaller id), tiles decided by their
+ * label summary, tiles processed, cross-tile unions attempted, longest parent walk seen}.
+ *   Refusals, all before anything is written: MGC_ERR_INVALID for a NULL handle, a side or full other than 0 / 1, a negative cap
+ * or a table pointer missing with cap > 0; MGC_ERR_UNSUPPORTED on a slab handle and for volumes of 2^32 - 1 voxels or more (parents
+ * are 32-bit); MGC_ERR_STATE with labels NULL outside the states of mgc_cut_sets.  Changes nothing on the handle: every block of the
+ * call comes from the pool and goes back; labels, snapshot, markers, residual graph, statistics, launch counts, device_bytes stay. */
+int mgc_components(mgc_handle h, const uint8_t* labels, int side, int full, int32_t* ids, int64_t cap, int64_t* first, int64_t* size, uint8_t* flags, int64_t* out8);
+
+/* A label plane cleaned by components, in two steps.  1: of the foreground components at the fg_full neighbourhood those
+ * PASS that hold at least min_size (>= 1) voxels and, if seeded, a foreground marker of the handle; if largest > 0 only the `largest`
+ * biggest of them survive, ties on size going to the smaller id (0: no limit).  2, if fill_holes: the background components of the
+ * result at the hole_full neighbourhood that neither touch the border of the volume nor hold a background marker become foreground.
+ *   out (nvox bytes or NULL): the cleaned plane, 0 / 1.  changed_ids (cap entries or NULL): the ascending ids of the voxels whose
+ * being foreground changed.  out8 (or NULL) = {foreground components, survivors, voxels removed, cavities filled, voxels filled,
+ * voxels changed, 1 if the list was written (0: more than cap, or no list asked for: only the count is valid), 0}.
+ *   The plane, the states and the side effects (none) are those of mgc_components; MGC_ERR_INVALID also for a NULL rule,
+ * min_size < 1, largest < 0, a rule flag other than 0 / 1, a negative cap. */
+typedef struct { int32_t fg_full, seeded, fill_holes, hole_full; int64_t min_size, largest; } mgc_clean_rule;
+int mgc_clean_labels(mgc_handle h, const uint8_t* labels, const mgc_clean_rule* rule, uint8_t* out, int64_t cap, int64_t* changed_ids, int64_t* out8);
+
 /* Runs the n-link / t-link kernels: the residual graph is now resident in HBM. */
 int mgc_build(mgc_handle h);
 

@@ -86,6 +86,12 @@ def assert_valid(v, rel=1e-9):
     return diff / scale
 
 
+class CleanRule(C.Structure):
+    """mgc_clean_rule (include/medpy_hip.h): the rule of mgc_clean_labels"""
+    _fields_ = [("fg_full", C.c_int32), ("seeded", C.c_int32), ("fill_holes", C.c_int32), ("hole_full", C.c_int32), ("min_size", C.c_int64),
+                ("largest", C.c_int64)]
+
+
 class SlabStats(C.Structure):
     """mgc_slab_stats (include/medpy_hip.h): what mgc_solve_slab did"""
     _fields_ = [("outer", C.c_int64), ("relabel_passes", C.c_int64), ("phases", C.c_int64), ("exchanges", C.c_int64),
@@ -157,6 +163,8 @@ SIGNATURES = {
     "mgc_add_tweights_binned": (_INT, [_VP, _I64, _DBL, _DBL, _VP, _VP]),
     "mgc_update_tweights_binned": (_INT, [_VP, _I64, _DBL, _DBL, _VP, _VP]),
     "mgc_label_histograms": (_INT, [_VP, _VP, _I64, _DBL, _DBL, _VP, _VP, _VP]),
+    "mgc_components": (_INT, [_VP, _VP, _INT, _INT, _VP, _I64, _VP, _VP, _VP, _VP]),
+    "mgc_clean_labels": (_INT, [_VP, _VP, C.POINTER(CleanRule), _VP, _I64, _VP, _VP]),
     "mgc_build": (_INT, [_VP]),
     "mgc_get_nweights": (_INT, [_VP, _INT, _VP]),
     "mgc_get_tweights": (_INT, [_VP, _VP]),

@@ -3,7 +3,9 @@
 Same positional arguments, options and flow as reference bin/medpy_graphcut_voxel.py:77-249
 (``sigma badditional markers output [--boundary ...] [-s] [-f] [-v] [-d]``); the differences are the I/O layer
 (``medpy_amd.io`` instead of SimpleITK: .npy / NIfTI-1) and the read-out (bulk ``labels()`` instead of one
-``what_segment`` call per voxel, :177-181).  ``--connectivity`` is an extension (full neighbourhood).
+``what_segment`` call per voxel, :177-181).  ``--connectivity`` is an extension (full neighbourhood), and so are
+``--keep-seeded``, ``--keep-largest N``, ``--min-size N`` and ``--fill-holes``: the cut cleaned by its connected components on
+the device (``VoxelGraph.clean_labels``) before it is written.  Without them the script does what it always did.
 """
 import argparse
 import logging
@@ -74,12 +76,32 @@ def main(argv=None):
     logger.debug("Maxflow is {}".format(maxflow))
 
     logger.info("Applying results...")
-    result_image_data = gcgraph.labels()  # == the what_segment loop of the reference, all voxels at once
+    rule = clean_rule(args)
+    if rule is None:
+        result_image_data = gcgraph.labels()  # == the what_segment loop of the reference, all voxels at once
+    else:
+        logger.info("Cleaning the cut by its connected components: {}".format(rule))
+        result_image_data = gcgraph.clean_labels(**rule)
+        logger.debug("Cleaning: {}".format(gcgraph.clean_info()))
     result_image_data = numpy.asarray(result_image_data).reshape(bgmarkers_image_data.shape)
 
     save(result_image_data.astype(numpy.bool_), args.output, reference_header, args.force)
     logger.info("Successfully terminated.")
     return 0
+
+
+def clean_rule(args):
+    "The keyword arguments of ``clean_labels`` the flags ask for, or None when none of them is given."
+    if not (args.keep_seeded or args.fill_holes or args.keep_largest is not None or args.min_size is not None):
+        return None
+    return dict(seeded=args.keep_seeded, largest=args.keep_largest, min_size=1 if args.min_size is None else args.min_size, fill_holes=args.fill_holes)
+
+
+def _positive_int(text):
+    value = int(text)
+    if value < 1:
+        raise argparse.ArgumentTypeError("must be at least 1, got %s" % text)
+    return value
 
 
 def getArguments(parser, argv=None):
@@ -99,6 +121,13 @@ def getParser():
                              "while the ones prefixed with max_ require the gradient image.")
     parser.add_argument("--connectivity", type=int, default=None,
                         help="Extension: 2*ndim (default, the reference's neighbourhood) or 3**ndim-1 (8 / 26 neighbours).")
+    parser.add_argument("--keep-seeded", action="store_true",
+                        help="Extension: keep only the connected components of the foreground that hold a foreground marker.")
+    parser.add_argument("--keep-largest", type=_positive_int, default=None, metavar="N", help="Extension: keep only the N largest components of the foreground.")
+    parser.add_argument("--min-size", type=_positive_int, default=None, metavar="N", help="Extension: drop components of the foreground below N voxels.")
+    parser.add_argument("--fill-holes", action="store_true",
+                        help="Extension: fill the cavities of the foreground (background that neither touches the border of the image nor "
+                             "holds a background marker).")
     parser.add_argument("-s", dest="spacing", action="store_true",
                         help="Set this flag to take the pixel spacing of the image into account. The spacing data will be "
                              "extracted from the baddtional image.")

@@ -92,3 +92,6 @@ int mgc_label_histograms(mgc_handle h, const uint8_t* labels, int64_t nbins, dou
 }
 
 } /* extern "C" */
+
+/* (behind the kernel of this file as well: the connected components, DESIGN 16 -- the last code of the library) */
+#include "mgc_cc_driver.inl"

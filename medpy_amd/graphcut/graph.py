@@ -18,6 +18,7 @@ from .histogram import histogram_binning, histogram_bins, histogram_tables   # n
 
 
 CutSets = collections.namedtuple("CutSets", ("from_source", "to_sink", "ambiguous", "info"))   # what ``cut_sets()`` of every graph kind returns
+Components = collections.namedtuple("Components", ("ids", "first", "size", "flags", "info"))   # what ``VoxelGraph.components()`` returns
 ULP64 = 64 * 2.0 ** -52   # the rounding granularity of the project's parity statement, for the ``tol`` of VoxelGraph.source_side & co.
 
 
@@ -410,6 +411,7 @@ class VoxelGraph(object):
         self._nodes = int(numpy.prod(self._shape))
         self._labels = None
         self._table_facts = FACTS_UNKNOWN
+        self._full_neighbourhood = bool(connectivity) and connectivity != 2 * nd
         _lib.apply_env_params(self._h)
 
     # -- life cycle
@@ -963,6 +965,108 @@ class VoxelGraph(object):
         """``cut_is_unique(tol)`` under the name every graph kind has"""
         return self.cut_is_unique(tol)
 
+    # -- connected components of the cut, and the cut cleaned by them (DESIGN 16)
+    COMPONENTS_INFO_KEYS = ("components", "voxels", "largest_size", "largest_id", "tiles_skipped", "tiles_processed", "unions", "longest_walk")
+    CLEAN_INFO_KEYS = ("fg_components", "survivors", "voxels_removed", "cavities_filled", "voxels_filled", "voxels_changed", "list_written")
+    COMPONENTS_TABLE = 65536       # rows the first call of ``components()`` asks for
+    CLEAN_LIST = 1 << 20           # ids ``clean_labels(changed_only=True)`` reads back before it falls back to the volume
+    _clean_info = None             # out8 of the last clean_labels
+
+    def _cc_plane(self, what, labels):
+        if labels is None:
+            return None
+        if not (isinstance(labels, numpy.ndarray) and labels.dtype in (numpy.bool_, numpy.uint8) and labels.shape == self._shape):
+            raise ValueError("%s: labels must be None or a bool / uint8 array of shape %s" % (what, self._shape))
+        return self._marker_bytes(labels)
+
+    def _cc_full(self, what, name, connectivity, default):
+        if connectivity is None:
+            return int(default)
+        if isinstance(connectivity, str) and connectivity in ("face", "full"):
+            return int(connectivity == "full")
+        raise ValueError("%s: %s must be None, \"face\" or \"full\", got %r" % (what, name, connectivity))
+
+    def components(self, labels=None, foreground=True, connectivity=None, ids=True):
+        """``Components(ids, first, size, flags, info)``: the connected components of the foreground (``foreground=False``: of the
+        background) of a segmentation, labelled on the device (mgc_components).  ``labels`` of None: the graph's current cut, read
+        where it lies on the device (MedpyHipError ERR_STATE unless a converged ``maxflow()`` is current); otherwise a bool or uint8
+        array of the volume's shape, not zero = foreground, which goes up for this call only -- the call then works before the graph
+        is built too.  ``connectivity``: ``"face"`` (2 / 4 / 6 neighbours), ``"full"`` (2 / 8 / 26) or None, the graph's own.
+
+        The components are numbered 1..K in ascending order of their first voxel, the numbering of ``scipy.ndimage.label``.
+        ``ids``: int32 array of the volume's shape, 0 on the other side -- or None with ``ids=False``, when no volume comes down.
+        ``first`` / ``size`` (int64) and ``flags`` (uint8) have K entries: first voxel id, voxel count, and bits 1 = holds a
+        foreground marker of the graph, 2 = holds a background marker, 4 = touches the border of the volume.  ``info``: K, the voxels
+        of that side, size and id of the largest component, and counts of the device's work.  Not cached; nothing on the graph changes."""
+        plane = self._cc_plane("components", labels)
+        full = self._cc_full("components", "connectivity", connectivity, self._full_neighbourhood)
+        vol = numpy.empty(self._nodes, dtype=numpy.int32) if ids else None
+        cap = self.COMPONENTS_TABLE
+        while True:
+            first, size = numpy.zeros(cap, dtype=numpy.int64), numpy.zeros(cap, dtype=numpy.int64)
+            flags = numpy.zeros(cap, dtype=numpy.uint8)
+            out8 = numpy.zeros(8, dtype=numpy.int64)
+            self._call("mgc_components", None if plane is None else _lib.ptr(plane), int(bool(foreground)), full, None if vol is None else _lib.ptr(vol), cap,
+                       _lib.ptr(first), _lib.ptr(size), _lib.ptr(flags), _lib.ptr(out8))
+            k = int(out8[0])
+            if k <= cap:
+                break
+            cap = k   # the table held the first rows only: once more, with room for all
+        return Components(None if vol is None else vol.reshape(self._shape), first[:k], size[:k], flags[:k], dict(zip(self.COMPONENTS_INFO_KEYS, out8.tolist())))
+
+    def clean_labels(self, labels=None, min_size=1, largest=None, seeded=False, fill_holes=False, connectivity=None, hole_connectivity=None, out=None,
+                     changed_only=False):
+        """The segmentation cleaned by components, on the device (mgc_clean_labels), in two steps.  1: of the foreground components
+        at ``connectivity`` (None: the graph's own) those pass that hold at least ``min_size`` voxels and, with ``seeded``, a
+        foreground marker of the graph; with ``largest=n`` only the n biggest of them survive, ties on size going to the one whose
+        first voxel comes first.  2, with ``fill_holes``: the background components of the result at ``hole_connectivity`` (None:
+        ``"face"``) that neither touch the border of the volume nor hold a background marker become foreground -- a background
+        marker inside a cavity keeps it open.  ``labels`` as in ``components()``.
+
+        Returns the cleaned bool volume (written into ``out``, a writeable C-contiguous bool array of the volume's shape, when
+        given).  ``changed_only=True``: the ascending int64 ids of the voxels the rule changed instead, and no volume comes down
+        unless there are more than ``CLEAN_LIST`` of them.  ``clean_info()`` has the counts.  Nothing on the graph changes."""
+        plane = self._cc_plane("clean_labels", labels)
+        default_full = self._full_neighbourhood
+        rule = _lib.CleanRule(self._cc_full("clean_labels", "connectivity", connectivity, default_full), int(bool(seeded)), int(bool(fill_holes)),
+                              self._cc_full("clean_labels", "hole_connectivity", hole_connectivity, False), 1, 0)
+        for name, v, lo in (("min_size", min_size, 1), ("largest", 1 if largest is None else largest, 1)):
+            if isinstance(v, (bool, numpy.bool_)) or not isinstance(v, (int, numpy.integer)) or v < lo:
+                raise ValueError("clean_labels: %s must be an integer >= %d, got %r" % (name, lo, v))
+        rule.min_size, rule.largest = int(min_size), 0 if largest is None else int(largest)
+        if out is not None and not (isinstance(out, numpy.ndarray) and out.shape == self._shape and out.dtype == numpy.bool_ and out.flags.c_contiguous
+                                    and out.flags.writeable):
+            raise ValueError("clean_labels(out=...): a writeable C-contiguous bool array of shape %s" % (self._shape,))
+        out8 = numpy.zeros(8, dtype=numpy.int64)
+        src = None if plane is None else _lib.ptr(plane)
+        if changed_only:
+            cap = int(self.CLEAN_LIST)
+            ids = numpy.zeros(max(cap, 1), dtype=numpy.int64)
+            self._call("mgc_clean_labels", src, C.byref(rule), None, cap, _lib.ptr(ids), _lib.ptr(out8))
+            self._clean_info = out8
+            if out8[6]:
+                return ids[:int(out8[5])].copy()
+            # more changes than the list holds (rare: the list takes a million ids): the cleaned volume comes down after all, next to
+            # the plane it was cleaned from, and the ids are computed here.  The cut's labels are read into an array of this call:
+            # nothing the graph caches is touched.
+            vol = numpy.empty(self._nodes, dtype=numpy.uint8)
+            self._call("mgc_clean_labels", src, C.byref(rule), _lib.ptr(vol), 0, None, _lib.ptr(out8))
+            self._clean_info = out8
+            before = plane.reshape(-1) if plane is not None else numpy.empty(self._nodes, dtype=numpy.uint8)
+            if plane is None:
+                self._call("mgc_labels", _lib.ptr(before))
+            return numpy.flatnonzero((vol != 0) != (before != 0)).astype(numpy.int64)
+        vol = numpy.empty(self._nodes, dtype=numpy.uint8) if out is None else out.reshape(-1).view(numpy.uint8)
+        self._call("mgc_clean_labels", src, C.byref(rule), _lib.ptr(vol), 0, None, _lib.ptr(out8))
+        self._clean_info = out8
+        return vol.view(numpy.bool_).reshape(self._shape) if out is None else out
+
+    def clean_info(self):
+        """of the last ``clean_labels``: ``fg_components``, ``survivors``, ``voxels_removed`` (step 1), ``cavities_filled``,
+        ``voxels_filled`` (step 2), ``voxels_changed``, and ``list_written``: 1 when the device wrote the list of changed ids"""
+        out8 = self._clean_info if self._clean_info is not None else numpy.zeros(8, dtype=numpy.int64)
+        return dict(zip(self.CLEAN_INFO_KEYS, out8.tolist()))
+
     def what_segment(self, i):
         """Graph::what_segment, reference graph.h:561-571."""
         seg = C.c_int(0)
@@ -1163,6 +1267,23 @@ class SparseGraph(object):
     def cut_sets_info(self, tol=None):
         """The ambiguity set exists for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
         self._no_cut_sets("cut_sets_info")
+
+    def _no_components(self, what):
+        raise NotImplementedError("medpy_amd: %s is implemented for the voxel lattice solver (1-D..3-D volumes, VoxelGraph) only: the "
+                                  "components are those of a label plane on the voxel lattice, and this graph went to the sparse-graph solver" % what)
+
+    def components(self, labels=None, foreground=True, connectivity=None, ids=True):
+        """Connected components exist for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
+        self._no_components("components")
+
+    def clean_labels(self, labels=None, min_size=1, largest=None, seeded=False, fill_holes=False, connectivity=None, hole_connectivity=None, out=None,
+                     changed_only=False):
+        """Cleaning by components exists for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
+        self._no_components("clean_labels")
+
+    def clean_info(self):
+        """Cleaning by components exists for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
+        self._no_components("clean_info")
 
     # -- the other minimum cuts (DESIGN 13c)
     CUT_SETS_INFO_KEYS = ("from_source", "to_sink", "ambiguous", "forward_passes", "forward_seeds", "backward_passes", "backward_seeds",
@@ -1876,6 +1997,19 @@ class EmbeddedLatticeGraph(object):
 
     def cut_sets_unique(self, tol=None):
         return self.cut_is_unique(tol)
+
+    def components(self, labels=None, foreground=True, connectivity=None, ids=True):
+        """of the lattice part (``VoxelGraph.components``): arrays in the lattice's shape, ids of lattice voxels; the isolated nodes
+        behind the lattice have no neighbours and are left out"""
+        return self._inner.components(labels, foreground, connectivity, ids)
+
+    def clean_labels(self, labels=None, min_size=1, largest=None, seeded=False, fill_holes=False, connectivity=None, hole_connectivity=None, out=None,
+                     changed_only=False):
+        """of the lattice part (``VoxelGraph.clean_labels``), in the lattice's shape"""
+        return self._inner.clean_labels(labels, min_size, largest, seeded, fill_holes, connectivity, hole_connectivity, out, changed_only)
+
+    def clean_info(self):
+        return self._inner.clean_info()
 
     def stats(self):
         return self._inner.stats()
