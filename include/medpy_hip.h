@@ -412,6 +412,33 @@ int mgc_components(mgc_handle h, const uint8_t* labels, int side, int full, int3
 typedef struct { int32_t fg_full, seeded, fill_holes, hole_full; int64_t min_size, largest; } mgc_clean_rule;
 int mgc_clean_labels(mgc_handle h, const uint8_t* labels, const mgc_clean_rule* rule, uint8_t* out, int64_t cap, int64_t* changed_ids, int64_t* out8);
 
+/* The exact Euclidean distance transform of a byte plane on the handle's lattice, and the overlap and surface measures of two planes
+ * (DESIGN 17): what scoring a cut against a ground truth needs, where the cut lies.  A plane is one byte per voxel in C order on the
+ * host, any byte but 0 being foreground (any single handle, built or not), or NULL: the labels of the current cut (the states of
+ * mgc_cut_sets, MGC_ERR_STATE otherwise).  spacing: NULL = unity, else ndim finite positive doubles, one per axis of the handle.
+ *   mgc_distance_transform: the seeds are the voxels of `side` (1: not zero, 0: zero).  out_sq[v] (nvox doubles in C order, or NULL:
+ * only the counts) = the minimum over the seeds s of fl(fl(fl(a_{n-1}^2) + fl(a_{n-2}^2)) + fl(a_{n-3}^2)), a_k = fl(spacing_k *
+ * (v_k - s_k)): the SQUARED distance in f64, the axes added from the last to the first, every operation rounded on its own (no fused
+ * multiply-add).  0 on the seeds, +inf everywhere without a seed.  out4 (or NULL) = {seeds, lines that were longer than the 512
+ * voxels a panel of on-chip memory takes and went the slower way through device memory, 0, 0}.
+ *   mgc_surface_distances: the border of an object X at `connectivity` (1 .. ndim, the structuring element of
+ * scipy.ndimage.generate_binary_structure(ndim, connectivity)) is every voxel of X with a neighbour that is background or outside the
+ * volume -- X ^ binary_erosion(X, structure).  Only the axes of the handle give neighbours: a 2-D handle has none along z, a 3-D handle
+ * of shape (1, Y, X) has them, all outside.  sds_sq (cap doubles; NULL allowed when cap is 0) takes the SQUARED distance from each border
+ * voxel of a to the nearest border voxel of b, in ascending voxel id, the first cap of them; the caller takes the root.  out8 (or NULL) =
+ * {border voxels of a, border voxels of b, voxels of a, voxels of b, lines that went the slower way, 0, 0, 0}.  An empty a or b is no
+ * error: nothing is written and the counts say so.  b must not be NULL.
+ *   mgc_overlap_counts: out4 = {tp, fp, fn, tn} of a against b: voxels of both, of a only, of b only, of neither.  Exact integers,
+ * summed in a fixed order.
+ *   Refusals, all before anything is written: MGC_ERR_INVALID for a NULL handle, a side other than 0 / 1, a connectivity outside
+ * 1 .. ndim, a spacing that is not finite and positive, a negative cap, sds_sq NULL with cap > 0, b or the out4 of mgc_overlap_counts
+ * NULL; MGC_ERR_UNSUPPORTED on a slab handle; MGC_ERR_STATE with a NULL plane outside the states of mgc_cut_sets.  Changes nothing on
+ * the handle: every block of a call comes from the pool and goes back; labels, snapshot, markers, residual graph, statistics, launch
+ * counts, device_bytes stay. */
+int mgc_distance_transform(mgc_handle h, const uint8_t* plane, int side, const double* spacing, double* out_sq, int64_t* out4);
+int mgc_surface_distances(mgc_handle h, const uint8_t* a, const uint8_t* b, int connectivity, const double* spacing, int64_t cap, double* sds_sq, int64_t* out8);
+int mgc_overlap_counts(mgc_handle h, const uint8_t* a, const uint8_t* b, int64_t* out4);
+
 /* Runs the n-link / t-link kernels: the residual graph is now resident in HBM. */
 int mgc_build(mgc_handle h);
 

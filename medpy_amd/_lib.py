@@ -165,6 +165,9 @@ SIGNATURES = {
     "mgc_label_histograms": (_INT, [_VP, _VP, _I64, _DBL, _DBL, _VP, _VP, _VP]),
     "mgc_components": (_INT, [_VP, _VP, _INT, _INT, _VP, _I64, _VP, _VP, _VP, _VP]),
     "mgc_clean_labels": (_INT, [_VP, _VP, C.POINTER(CleanRule), _VP, _I64, _VP, _VP]),
+    "mgc_distance_transform": (_INT, [_VP, _VP, _INT, _VP, _VP, _VP]),
+    "mgc_surface_distances": (_INT, [_VP, _VP, _VP, _INT, _VP, _I64, _VP, _VP]),
+    "mgc_overlap_counts": (_INT, [_VP, _VP, _VP, _VP]),
     "mgc_build": (_INT, [_VP]),
     "mgc_get_nweights": (_INT, [_VP, _INT, _VP]),
     "mgc_get_tweights": (_INT, [_VP, _VP]),

@@ -249,3 +249,6 @@ int mgc_clean_labels(mgc_handle h, const uint8_t* labels, const mgc_clean_rule* 
 }
 
 } /* extern "C" */
+
+/* (behind the kernels of this file as well: the distance transform and the surface metrics, DESIGN 17 -- the last code of the library) */
+#include "mgc_edt_driver.inl"

@@ -1067,6 +1067,89 @@ class VoxelGraph(object):
         out8 = self._clean_info if self._clean_info is not None else numpy.zeros(8, dtype=numpy.int64)
         return dict(zip(self.CLEAN_INFO_KEYS, out8.tolist()))
 
+    # -- the Euclidean distance transform of a segmentation and its overlap and surface measures against another
+    SURFACE_LIST = 1 << 20         # distances the first call of ``surface_distances()`` asks for
+    _edt_info = None               # out4 of the last distance_transform
+
+    def _edt_plane(self, what, name, plane):
+        if not (isinstance(plane, numpy.ndarray) and plane.dtype in (numpy.bool_, numpy.uint8) and plane.shape == self._shape):
+            raise ValueError("%s: %s must be a bool / uint8 array of shape %s" % (what, name, self._shape))
+        return self._marker_bytes(plane)
+
+    def _edt_spacing(self, what, spacing):
+        if spacing is None:
+            return None
+        sp = numpy.asarray(spacing, dtype=numpy.float64)
+        if sp.ndim == 0:
+            sp = numpy.full(len(self._shape), float(sp))
+        if sp.shape != (len(self._shape),):
+            raise ValueError("%s: the spacing must be a scalar or %d values, got %r" % (what, len(self._shape), spacing))
+        if not (numpy.isfinite(sp).all() and (sp > 0).all()):
+            raise ValueError("%s: the spacing must be finite and positive, got %r" % (what, spacing))
+        return numpy.ascontiguousarray(sp)
+
+    def distance_transform(self, labels=None, to="foreground", spacing=None, squared=False):
+        """float64 array of the volume's shape: the exact Euclidean distance of every voxel to the nearest foreground voxel of a
+        segmentation (``to="background"``: to the nearest background voxel -- scipy.ndimage.distance_transform_edt of the
+        segmentation), computed on the device (mgc_distance_transform).  ``labels`` as in ``components()``; ``spacing``: None, a
+        scalar or one value per axis.  ``squared=True`` returns what the device computes: the minimum over the seeds of
+        ``(sx * dx) ** 2 + (sy * dy) ** 2 + (sz * dz) ** 2`` in float64, the last axis first, every operation rounded on its own --
+        exact integers at unit spacing; the root is NumPy's.  +inf everywhere when there is no such voxel.  ``edt_info()`` has the
+        counts.  Nothing on the graph changes."""
+        plane = None if labels is None else self._edt_plane("distance_transform", "labels", labels)
+        if to not in ("foreground", "background"):
+            raise ValueError("distance_transform: to must be \"foreground\" or \"background\", got %r" % (to,))
+        sp = self._edt_spacing("distance_transform", spacing)
+        out = numpy.empty(self._nodes, dtype=numpy.float64)
+        out4 = numpy.zeros(4, dtype=numpy.int64)
+        self._call("mgc_distance_transform", None if plane is None else _lib.ptr(plane), int(to == "foreground"), None if sp is None else _lib.ptr(sp), _lib.ptr(out),
+                   _lib.ptr(out4))
+        self._edt_info = out4
+        out = out.reshape(self._shape)
+        return out if squared else numpy.sqrt(out, out=out)
+
+    def edt_info(self):
+        """of the last ``distance_transform``: ``seeds``, and ``long_lines``, the lines that were too long for on-chip memory"""
+        out4 = self._edt_info if self._edt_info is not None else numpy.zeros(4, dtype=numpy.int64)
+        return {"seeds": int(out4[0]), "long_lines": int(out4[1])}
+
+    def surface_distances(self, reference, labels=None, voxelspacing=None, connectivity=1):
+        """float64 list: the distance from every border voxel of the segmentation to the nearest border voxel of ``reference``, in
+        ascending voxel id -- ``dt[result_border]`` of the reference's surface measures, from which ``hd``, ``asd`` and their kin
+        follow (medpy_amd.metric.binary).  Borders, transform and gathering run on the device (mgc_surface_distances); the root is
+        NumPy's.  ``connectivity``: 1 .. ndim, as in scipy.ndimage.generate_binary_structure.  RuntimeError when either object is
+        empty.  Nothing on the graph changes."""
+        ref = self._edt_plane("surface_distances", "reference", reference)
+        plane = None if labels is None else self._edt_plane("surface_distances", "labels", labels)
+        if isinstance(connectivity, (bool, numpy.bool_)) or not isinstance(connectivity, (int, numpy.integer)) or not 1 <= connectivity <= len(self._shape):
+            raise ValueError("surface_distances: connectivity must be an integer 1 .. %d, got %r" % (len(self._shape), connectivity))
+        sp = self._edt_spacing("surface_distances", voxelspacing)
+        cap = int(self.SURFACE_LIST)
+        while True:
+            sds = numpy.empty(max(cap, 1), dtype=numpy.float64)
+            out8 = numpy.zeros(8, dtype=numpy.int64)
+            self._call("mgc_surface_distances", None if plane is None else _lib.ptr(plane), _lib.ptr(ref), int(connectivity), None if sp is None else _lib.ptr(sp), cap,
+                       _lib.ptr(sds), _lib.ptr(out8))
+            if out8[2] == 0:
+                raise RuntimeError("The first supplied array does not contain any binary object.")
+            if out8[3] == 0:
+                raise RuntimeError("The second supplied array does not contain any binary object.")
+            n = int(out8[0])
+            if n <= cap:
+                break
+            cap = n   # the list held the first entries only: once more, with room for all
+        sds = sds[:n]
+        return numpy.sqrt(sds, out=sds)
+
+    def overlap_counts(self, reference, labels=None):
+        """``(tp, fp, fn, tn)``: the voxels of the segmentation and of ``reference``, of the segmentation only, of ``reference``
+        only, of neither -- counted on the device (mgc_overlap_counts).  Nothing on the graph changes."""
+        ref = self._edt_plane("overlap_counts", "reference", reference)
+        plane = None if labels is None else self._edt_plane("overlap_counts", "labels", labels)
+        out4 = numpy.zeros(4, dtype=numpy.int64)
+        self._call("mgc_overlap_counts", None if plane is None else _lib.ptr(plane), _lib.ptr(ref), _lib.ptr(out4))
+        return tuple(int(v) for v in out4)
+
     def what_segment(self, i):
         """Graph::what_segment, reference graph.h:561-571."""
         seg = C.c_int(0)
@@ -1284,6 +1367,22 @@ class SparseGraph(object):
     def clean_info(self):
         """Cleaning by components exists for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
         self._no_components("clean_info")
+
+    def _no_metrics(self, what):
+        raise NotImplementedError("medpy_amd: %s is implemented for the voxel lattice solver (1-D..3-D volumes, VoxelGraph) only: distances "
+                                  "are those between the voxels of a lattice, and this graph went to the sparse-graph solver" % what)
+
+    def distance_transform(self, labels=None, to="foreground", spacing=None, squared=False):
+        """The distance transform exists for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
+        self._no_metrics("distance_transform")
+
+    def surface_distances(self, reference, labels=None, voxelspacing=None, connectivity=1):
+        """Surface distances exist for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
+        self._no_metrics("surface_distances")
+
+    def overlap_counts(self, reference, labels=None):
+        """Overlap counts exist for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
+        self._no_metrics("overlap_counts")
 
     # -- the other minimum cuts (DESIGN 13c)
     CUT_SETS_INFO_KEYS = ("from_source", "to_sink", "ambiguous", "forward_passes", "forward_seeds", "backward_passes", "backward_seeds",
@@ -2010,6 +2109,18 @@ class EmbeddedLatticeGraph(object):
 
     def clean_info(self):
         return self._inner.clean_info()
+
+    def distance_transform(self, labels=None, to="foreground", spacing=None, squared=False):
+        """of the lattice part (``VoxelGraph.distance_transform``), in the lattice's shape"""
+        return self._inner.distance_transform(labels, to, spacing, squared)
+
+    def surface_distances(self, reference, labels=None, voxelspacing=None, connectivity=1):
+        """of the lattice part (``VoxelGraph.surface_distances``)"""
+        return self._inner.surface_distances(reference, labels, voxelspacing, connectivity)
+
+    def overlap_counts(self, reference, labels=None):
+        """of the lattice part (``VoxelGraph.overlap_counts``)"""
+        return self._inner.overlap_counts(reference, labels)
 
     def stats(self):
         return self._inner.stats()
