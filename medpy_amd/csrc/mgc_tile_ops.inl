@@ -386,8 +386,10 @@ MGC_HD void mgc_discharge_tile(X& x, const MgcLattice& L, int tile, uint32_t pha
         mgc_load_nbrs(x, L, tile, t);
         mgc_load_halo_inbox(x, L, tile, t);
         /* (depflag is free during a discharge) face t of this tile still carries its outbox flag: flow that the wave form held back without
-         * waking the neighbour (MGCW_HOLD_THIN, mgc_wave_ops.inl) may wait there, and what this visit pushes across the face is added to it */
-        if (t < 6 && x.S.nbr[t] >= 0 && mgc_owned(L, x.S.nbr[t])) x.S.depflag[t] = (int32_t)((L.oflags[tile] >> t) & 1u);
+         * waking the neighbour (MGCW_HOLD_THIN, mgc_wave_ops.inl) may wait there, and what this visit pushes across the face is added to it.
+         * A GHOST neighbour never comes for its flow: the next border message takes it (mgc_halo_pack_tile clears the flag and the
+         * slots), and with exchange_rounds > 1 this tile can be discharged twice before that message goes out */
+        if (t < 6 && x.S.nbr[t] >= 0) x.S.depflag[t] = (int32_t)((L.oflags[tile] >> t) & 1u);
         ob0[t] = ob1[t] = ob2[t] = 0.0;
         lostarc[t] = 0;
         if (!(st_now & MGC_ST_SINK)) snk[t] = 0.0; /* the build writes the sink plane only where a tile has a sink link */
@@ -593,7 +595,8 @@ MGC_HD void mgc_discharge_tile(X& x, const MgcLattice& L, int tile, uint32_t pha
         t_rmask[(unsigned)t] = (uint8_t)m;
         t_height[(unsigned)t] = x.S.hs[mgc_hs_index(z, y, xx)];
         /* plain stores: the neighbour emptied these slots when it last absorbed, and it always runs (or absorb_all
-         * does) between two of our discharges -- unless the wave form held thin flow back (depflag, see the load) */
+         * does) between two of our discharges -- unless the wave form held thin flow back, or the neighbour is a ghost tile whose
+         * border message has not gone out yet (depflag, see the load) */
         auto put = [&](int f, int k, double ob) {
             double* slot = &t_obox[(unsigned)(f * MGC_TF + k)];
             *slot = x.S.depflag[f] ? ob + *slot : ob;

@@ -287,6 +287,9 @@ MGC_HD void mgcw_discharge_impl(W& w, const MgcLattice& L, int tile, uint32_t ph
     int32_t* const t_height = L.height + (int64_t)tile * MGC_TV;
     int tz, ty, tx;
     mgc_tile_coords(L, tile, tz, ty, tx);
+    /* (wave-uniform; 0 on a single handle) the z faces behind which a GHOST tile lies.  A ghost never comes for the flow in our outbox: the
+     * next border message takes it (mgc_halo_pack_tile), and with exchange_rounds > 1 this tile can be visited twice before that goes out */
+    const uint32_t ghostface = ((L.tz_own_lo > 0 && tz == L.tz_own_lo) ? 16u : 0u) | ((L.tz_own_hi < L.gz && tz == L.tz_own_hi - 1) ? 32u : 0u);
 
     /* ---- one trip to HBM: label halo + inbox (issued first, see mgcw_halo_issue), own state ---- */
     typename W::template Reg<int, 6> hv;
@@ -296,7 +299,7 @@ MGC_HD void mgcw_discharge_impl(W& w, const MgcLattice& L, int tile, uint32_t ph
     w.lanes([&](int l) MGCW_INL {
         mgcw_halo_issue(w, L, tile, l, hv, dnb, ofl);
         st0(l, 0) = (int)L.status[tile];
-        if ((flags & MGCW_HOLD_THIN) && l == 6) ofl(l, 0) = (int)L.oflags[tile]; /* lane 6: this tile's own flags -- flow held back by an earlier visit may still wait in its outbox (see the tail) */
+        if (((flags & MGCW_HOLD_THIN) || ghostface) && l == 6) ofl(l, 0) = (int)L.oflags[tile]; /* lane 6: this tile's own flags -- flow held back by an earlier visit, or not yet taken across a slab border, may still wait in its outbox (see the tail) */
         mgcw_static_for<8>([&](auto KK) MGCW_INL {
             constexpr int K = decltype(KK)::value;
             e(l, K) = w.ld(t_excess, K * 64 + l);
@@ -626,6 +629,13 @@ MGC_HD void mgcw_discharge_impl(W& w, const MgcLattice& L, int tile, uint32_t ph
         for (int f = 0; f < 6; ++f)
             if (((face >> f) & 1u) && w.any([&](int l) MGCW_INL -> bool { return l == 6 && (((uint32_t)ofl(l, 0) >> f) & 1u); })) carry |= 1u << f;
     }
+    if (face & ghostface) { /* Z-slabs: what an earlier visit pushed over the slab border and no border message has taken yet */
+#pragma unroll
+        for (int f = 4; f < 6; ++f)
+            if (((face & ghostface) >> f) & 1u) {
+                if (w.any([&](int l) MGCW_INL -> bool { return l == 6 && (((uint32_t)ofl(l, 0) >> f) & 1u); })) carry |= 1u << f;
+            }
+    }
     const int held = __builtin_popcount(face & ~wakeface); /* faces with flow whose neighbour is not woken (MGC_CNT_HELD_WAKEUPS) */
     /* lane l < 6 wakes the neighbour across face l, lane 6 this tile itself (budget exhausted with work left) */
     typename W::template Reg<int, 4> wk; /* tile to wake (-1: none), its list, claimed?, position */
@@ -703,7 +713,7 @@ MGC_HD void mgcw_discharge_impl(W& w, const MgcLattice& L, int tile, uint32_t ph
         w.S.inbox[4][l] = obz(l, 0);
         w.S.inbox[5][l] = obz(l, 1);
     });
-    if (carry) { /* (MGCW_HOLD_THIN, rare: a second visit before the neighbour came for what the first one held back) */
+    if (carry) { /* (MGCW_HOLD_THIN, or a ghost neighbour; rare: a second visit before anybody came for what the first one left) */
         w.lanes([&](int l) MGCW_INL {
 #pragma unroll
             for (int f = 0; f < 6; ++f)
@@ -756,7 +766,7 @@ MGC_HD void mgcw_discharge_impl(W& w, const MgcLattice& L, int tile, uint32_t ph
     w.mark(7); /* claims back, positions drawn, state / planes / labels stored */
     w.lanes([&](int l) MGCW_INL {
         /* outbox: plain stores -- the neighbour emptied these slots when it last absorbed, and it always runs (or
-         * absorb_all does) between two of our discharges */
+         * absorb_all does) between two of our discharges; where it does not, what waited was added above (carry) */
 #pragma unroll
         for (int f = 0; f < 6; ++f) {
             const double ob = w.S.inbox[f][l];
