@@ -439,6 +439,38 @@ int mgc_distance_transform(mgc_handle h, const uint8_t* plane, int side, const d
 int mgc_surface_distances(mgc_handle h, const uint8_t* a, const uint8_t* b, int connectivity, const double* spacing, int64_t cap, double* sds_sq, int64_t* out8);
 int mgc_overlap_counts(mgc_handle h, const uint8_t* a, const uint8_t* b, int64_t* out4);
 
+/* The geodesic distance transform on the lattice of a single handle, and the regional term on top of it (the definition is
+ * medpy_amd/csrc/mgc_geo.h).  full = 0: the face neighbourhood (2 / 4 / 6 neighbours), 1: the full one (2 / 8 / 26); neighbours outside
+ * the volume do not exist.  The arc between the neighbours p and q = p + d has the length, in f64 and every operation rounded on its
+ * own, w = e_d + gamma * |I_p - I_q| with e_d = step * sqrt(a_x^2 + a_y^2 + a_z^2) (x, the last array axis, first) and a_k =
+ * spacing_k * |d_k|; spacing NULL: unity, else ndim finite positive values; gamma and step finite and not negative; step = 0 gives the
+ * pure intensity geodesic.  I is the image of mgc_marker_histograms as f64 (the feature image, else the boundary image; every dtype);
+ * with gamma = 0 no image is read and none is needed.  D(v) = the minimum over the seeds and the lattice paths from a seed to v of the
+ * sum of the arc lengths added from the seed outwards: 0 on seeds, +inf where no seed connects -- the numbers of Dijkstra's algorithm
+ * with f64 additions, bit for bit, whatever the order in which the device relaxes (D is a least fixpoint).
+ *   mgc_geodesic_distance: source 0: seeds is a byte plane of the caller's (host, C order, any byte but 0 a seed; any single handle
+ * will do, built or not); source 1 / 2: the foreground / background markers where they lie on the device, seeds NULL (a plane that
+ * was never given has no seeds).  out: nvox doubles in C order or NULL.  out8 (or NULL) = {seeds, rounds (launches over the active
+ * tiles), tile visits, in-tile sweeps summed, visits that ended at the sweep cap, voxels with a finite distance, 0, 0}.  Changes
+ * nothing on the handle: every block of a call comes from the pool and goes back; labels, snapshot, markers, residual graph,
+ * statistics, launch counts, device_bytes stay.
+ *   mgc_add_tweights_geodesic: with D_F and D_B the transforms of the handle's foreground and background markers and t = D_F + D_B,
+ * voxel p gets one Graph::add_tweights(S, K): both infinite: (0, 0); only D_F infinite: (0, lam); only D_B infinite: (lam, 0); t == 0:
+ * (lam / 2, lam / 2); else (lam * (D_B / t), lam * (D_F / t)); lam finite and not negative.  The store is left exactly as
+ * mgc_add_tweights(h, S, K, MGC_F64) would leave it.  mgc_update_tweights_geodesic is the warm form: mgc_update_tweights of
+ * those arrays, except that the label snapshot of mgc_labels_delta is kept the way mgc_edit_tweights keeps it (the labels of a finished
+ * cut change hands; the snapshot of an edit the next solve has yet to see stays): a refit follows a stroke, and mgc_labels_delta after
+ * the next solve names the voxels the round changed.  The two planes live for the call only.  After a call that went through, mgc_last_error holds a note of where its
+ * time went (transform_ms, expand_ms, flow_const_ms, fold_ms; rounds and visits of the two transforms).
+ *   Refusals, before the first write and with the handle as it was: MGC_ERR_INVALID for a NULL handle, source outside 0..2, seeds NULL
+ * with source 0 or given with source 1 / 2, full other than 0 / 1, gamma, step or lam not finite or negative, a spacing not finite and
+ * positive, a value of a float image that is not finite (the message names the lowest flat index and the value); MGC_ERR_STATE with
+ * gamma > 0 and no image, and in the states in which mgc_add_tweights / mgc_update_tweights refuse; MGC_ERR_UNSUPPORTED on a slab
+ * handle; MGC_ERR_OOM before anything changed. */
+int mgc_geodesic_distance(mgc_handle h, const uint8_t* seeds, int source, int full, double gamma, double step, const double* spacing, double* out, int64_t* out8);
+int mgc_add_tweights_geodesic(mgc_handle h, int full, double gamma, double step, const double* spacing, double lam);
+int mgc_update_tweights_geodesic(mgc_handle h, int full, double gamma, double step, const double* spacing, double lam);
+
 /* Runs the n-link / t-link kernels: the residual graph is now resident in HBM. */
 int mgc_build(mgc_handle h);
 

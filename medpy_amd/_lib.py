@@ -168,6 +168,9 @@ SIGNATURES = {
     "mgc_distance_transform": (_INT, [_VP, _VP, _INT, _VP, _VP, _VP]),
     "mgc_surface_distances": (_INT, [_VP, _VP, _VP, _INT, _VP, _I64, _VP, _VP]),
     "mgc_overlap_counts": (_INT, [_VP, _VP, _VP, _VP]),
+    "mgc_geodesic_distance": (_INT, [_VP, _VP, _INT, _INT, _DBL, _DBL, _VP, _VP, _VP]),
+    "mgc_add_tweights_geodesic": (_INT, [_VP, _INT, _DBL, _DBL, _VP, _DBL]),
+    "mgc_update_tweights_geodesic": (_INT, [_VP, _INT, _DBL, _DBL, _VP, _DBL]),
     "mgc_build": (_INT, [_VP]),
     "mgc_get_nweights": (_INT, [_VP, _INT, _VP]),
     "mgc_get_tweights": (_INT, [_VP, _VP]),

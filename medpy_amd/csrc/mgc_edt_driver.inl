@@ -227,3 +227,6 @@ int mgc_overlap_counts(mgc_handle h, const uint8_t* a, const uint8_t* b, int64_t
 }
 
 } /* extern "C" */
+
+/* (behind the kernels of this file as well: the geodesic distance transform and its regional term, DESIGN 18 -- the last code of the library) */
+#include "mgc_geo_driver.inl"

@@ -7,7 +7,7 @@ arbitrary graphs (reference lib/maxflow/src/wrapper.cpp:27-134).
 """
 from . import energy_label, energy_voxel
 from .generate import graph_from_labels, graph_from_voxels
-from .energy_voxel import regional_histogram
+from .energy_voxel import regional_geodesic, regional_histogram
 from .graph import ULP64, Components, CutSets, GCGraph, Graph, GraphFloat, GraphInt, RegionGraph, SparseGraph, VoxelGraph, termtype
 from .histogram import histogram_binning, histogram_bins, histogram_tables
 from .write import graph_to_dimacs
@@ -17,4 +17,4 @@ GraphDouble = SparseGraph
 
 __all__ = ["graph_from_voxels", "graph_from_labels", "energy_voxel", "energy_label", "GCGraph", "VoxelGraph", "SparseGraph", "RegionGraph",
            "GraphDouble", "GraphFloat", "GraphInt", "Graph", "graph_to_dimacs", "termtype", "split_marker", "graphcut_stawiaski", "ULP64", "CutSets", "Components",
-           "regional_histogram", "histogram_binning", "histogram_bins", "histogram_tables"]
+           "regional_histogram", "regional_geodesic", "histogram_binning", "histogram_bins", "histogram_tables"]

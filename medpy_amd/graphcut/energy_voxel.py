@@ -17,7 +17,7 @@ __all__ = [
     "boundary_maximum_exponential", "boundary_difference_exponential",
     "boundary_maximum_division", "boundary_difference_division",
     "boundary_maximum_power", "boundary_difference_power",
-    "boundary_precomputed", "regional_precomputed", "regional_histogram",
+    "boundary_precomputed", "regional_precomputed", "regional_histogram", "regional_geodesic",
 ]
 
 
@@ -135,3 +135,19 @@ def regional_histogram(graph, xxx_todo_changeme11):
     (image, bins, lam, eps) = xxx_todo_changeme11
     _need_facade(graph)
     graph.record_regional_histogram(image, bins, lam, eps)
+
+
+def regional_geodesic(graph, xxx_todo_changeme12):
+    """Geodesic regional term (GeoS; Price et al., "Geodesic graph cut"; extension, no reference counterpart): with D_F and D_B
+    the geodesic distances of a voxel to the foreground and to the background markers -- shortest lattice paths whose arcs
+    cost ``step`` times their length plus ``gamma`` times the intensity step they cross -- every voxel gets the t-links
+    ``lam * D_B / (D_F + D_B)`` (source) and ``lam * D_F / (D_F + D_B)`` (sink).  Arguments ``(gamma, lam[, step[, spacing[,
+    connectivity[, image]]]])``: ``step`` defaults to 1, ``spacing`` to unity, ``connectivity`` (1 or the number of axes) to the
+    graph's own, ``image`` to the boundary term's image.  Distances and t-links are computed on the device from the resident
+    image and markers (``GCGraph.record_regional_geodesic``), and ``VoxelGraph.refit_regional_geodesic()`` fits the term again
+    after ``edit_markers``."""
+    args = tuple(xxx_todo_changeme12)
+    if not 2 <= len(args) <= 6:
+        raise ValueError("regional_geodesic takes (gamma, lam[, step[, spacing[, connectivity[, image]]]]), got {} values".format(len(args)))
+    _need_facade(graph)
+    graph.record_regional_geodesic(*args)

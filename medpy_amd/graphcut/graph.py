@@ -358,6 +358,13 @@ def _dense_array(shape, offset, w, what):
     return numpy.ascontiguousarray(w)
 
 
+class _GeodesicTerm(object):
+    """what ``GCGraph.record_regional_geodesic`` records: the parameters of the term and the image it reads (None: the boundary term's)"""
+
+    def __init__(self, gamma, lam, step, spacing, connectivity, image):
+        self.gamma, self.lam, self.step, self.spacing, self.connectivity, self.image = gamma, lam, step, spacing, connectivity, image
+
+
 class VoxelGraph(object):
     """What ``graph_from_voxels`` returns: the stand-in for ``maxflow.GraphDouble``.
 
@@ -1113,6 +1120,98 @@ class VoxelGraph(object):
         out4 = self._edt_info if self._edt_info is not None else numpy.zeros(4, dtype=numpy.int64)
         return {"seeds": int(out4[0]), "long_lines": int(out4[1])}
 
+    # -- the geodesic distance transform and the regional term on top of it
+    GEODESIC_INFO_KEYS = ("seeds", "rounds", "tile_visits", "sweeps", "capped_visits", "finite")
+    _geo_info = None               # out8 of the last geodesic_distance
+    _geo_params = None             # (gamma, lam, step, spacing, connectivity) of the geodesic term the graph was built with
+
+    def _geo_full(self, what, connectivity):
+        nd = len(self._shape)
+        if connectivity is None:
+            return int(self._full_neighbourhood)
+        if connectivity not in (1, nd):
+            raise ValueError("%s: connectivity must be 1 (face neighbours) or %d (the full neighbourhood), got %r" % (what, nd, connectivity))
+        return int(connectivity == nd and nd > 1)   # (on one axis the two neighbourhoods are the same)
+
+    @staticmethod
+    def _geo_number(what, name, v):
+        v = float(v)
+        if not (numpy.isfinite(v) and v >= 0):
+            raise ValueError("%s: %s must be finite and not negative, got %r" % (what, name, v))
+        return v
+
+    def geodesic_distance(self, seeds="fg", gamma=1.0, step=1.0, spacing=None, connectivity=None):
+        """float64 array of the volume's shape: the geodesic distance of every voxel to the nearest seed, computed on the device
+        (mgc_geodesic_distance).  The length of the arc between neighbours p and q at offset d is
+        ``step * sqrt(sum((spacing * d) ** 2)) + gamma * abs(I[p] - I[q])`` in float64, every operation rounded on its own, I the
+        feature image of the graph, else its boundary image (``gamma=0``: the chamfer distance, no image needed); the distance is
+        the smallest sum over the lattice paths from a seed, added from the seed outwards -- bit for bit what Dijkstra's
+        algorithm in float64 gives (tests/geodesic_cases.py states it).  0 on seeds, +inf where no seed connects.  ``seeds``:
+        ``"fg"`` / ``"bg"``, the markers of the graph where they lie on the device, or a bool / uint8 array of the volume's shape.
+        ``connectivity``: 1 (face neighbours) or the number of axes (the full neighbourhood); None: the graph's own.
+        ``spacing``: None, a scalar or one value per axis.  ``geodesic_info()`` has the counts.  Nothing on the graph changes."""
+        full = self._geo_full("geodesic_distance", connectivity)
+        gamma = self._geo_number("geodesic_distance", "gamma", gamma)
+        step = self._geo_number("geodesic_distance", "step", step)
+        sp = self._edt_spacing("geodesic_distance", spacing)
+        if isinstance(seeds, str):
+            if seeds not in ("fg", "bg"):
+                raise ValueError("geodesic_distance: seeds must be \"fg\", \"bg\" or an array, got %r" % (seeds,))
+            plane, source = None, 1 if seeds == "fg" else 2
+        else:
+            plane, source = self._edt_plane("geodesic_distance", "seeds", seeds), 0
+        out = numpy.empty(self._nodes, dtype=numpy.float64)
+        out8 = numpy.zeros(8, dtype=numpy.int64)
+        self._call("mgc_geodesic_distance", None if plane is None else _lib.ptr(plane), source, full, gamma, step, None if sp is None else _lib.ptr(sp), _lib.ptr(out),
+                   _lib.ptr(out8))
+        self._geo_info = out8
+        return out.reshape(self._shape)
+
+    def geodesic_info(self):
+        """of the last ``geodesic_distance``: ``seeds``, ``rounds`` (launches over the active tiles), ``tile_visits``, ``sweeps``
+        (summed over the visits), ``capped_visits`` (visits that ended at the sweep cap and woke their own tile) and ``finite``,
+        the voxels a seed reaches"""
+        out8 = self._geo_info if self._geo_info is not None else numpy.zeros(8, dtype=numpy.int64)
+        return dict(zip(self.GEODESIC_INFO_KEYS, out8.tolist()))
+
+    def _geo_term_args(self, what, gamma, lam, step, spacing, connectivity):
+        return (self._geo_number(what, "gamma", gamma), self._geo_number(what, "lam", lam), self._geo_number(what, "step", step),
+                self._edt_spacing(what, spacing), self._geo_full(what, connectivity))
+
+    def _add_tweights_geodesic(self, gamma, lam, step=1.0, spacing=None, connectivity=None):
+        """mgc_add_tweights_geodesic: one ``add_tweights(S[p], K[p])`` per voxel on the graph's explicit t-links, S and K the
+        geodesic term of the markers the graph holds -- what ``_add_tweights(*expected_term(D_F, D_B, lam))`` leaves, without
+        the arrays crossing the bus"""
+        gamma, lam, step, sp, full = self._geo_term_args("_add_tweights_geodesic", gamma, lam, step, spacing, connectivity)
+        self._labels = None
+        self._call("mgc_add_tweights_geodesic", full, gamma, step, None if sp is None else _lib.ptr(sp), lam)
+
+    def update_tweights_geodesic(self, gamma, lam, step=1.0, spacing=None, connectivity=None):
+        """Replace the explicit t-links by the geodesic term of the markers as they stand now -- what ``update_tweights_dense`` of
+        the term's two arrays leaves, bit for bit, with both transforms and the expansion on the device
+        (mgc_update_tweights_geodesic) -- and keep the residual graph: the next ``maxflow()`` is a warm solve.  Unlike
+        ``update_tweights_dense`` the call keeps the labels of the cut before it (or before the marker edit it follows) on the
+        device, so ``changed_labels()`` and ``labels(out=previous)`` work after that solve."""
+        self._refuse_host_merged("update_tweights_geodesic")
+        gamma, lam, step, sp, full = self._geo_term_args("update_tweights_geodesic", gamma, lam, step, spacing, connectivity)
+        self._labels = None
+        self._call("mgc_update_tweights_geodesic", full, gamma, step, None if sp is None else _lib.ptr(sp), lam)
+
+    def refit_regional_geodesic(self, gamma=None, lam=None):
+        """Fit the geodesic regional term (``energy_voxel.regional_geodesic``) to the markers as they stand now, after
+        ``update_markers`` / ``edit_markers``: both transforms run again on the device and the term replaces the explicit t-links.
+        ``gamma`` / ``lam`` of None: those the graph was built with; step, spacing and connectivity stay.  The next ``maxflow()``
+        is a warm solve with the labels and the flow of a graph built from the markers and the refitted term;
+        ``labels(out=previous)`` brings a copy of the previous labels up to date."""
+        self._refuse_host_merged("refit_regional_geodesic")
+        if self._geo_params is None:
+            raise ValueError("refit_regional_geodesic: the graph was built without a geodesic term (energy_voxel.regional_geodesic)")
+        g0, l0, step, spacing, connectivity = self._geo_params
+        gamma = g0 if gamma is None else gamma
+        lam = l0 if lam is None else lam
+        self.update_tweights_geodesic(gamma, lam, step, spacing, connectivity)
+        self._geo_params = (float(gamma), float(lam), step, spacing, connectivity)
+
     def surface_distances(self, reference, labels=None, voxelspacing=None, connectivity=1):
         """float64 list: the distance from every border voxel of the segmentation to the nearest border voxel of ``reference``, in
         ascending voxel id -- ``dt[result_border]`` of the reference's surface measures, from which ``hd``, ``asd`` and their kin
@@ -1383,6 +1482,18 @@ class SparseGraph(object):
     def overlap_counts(self, reference, labels=None):
         """Overlap counts exist for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
         self._no_metrics("overlap_counts")
+
+    def geodesic_distance(self, seeds="fg", gamma=1.0, step=1.0, spacing=None, connectivity=None):
+        """The geodesic distance transform exists for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
+        self._no_metrics("geodesic_distance")
+
+    def geodesic_info(self):
+        """The geodesic distance transform exists for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
+        self._no_metrics("geodesic_info")
+
+    def refit_regional_geodesic(self, gamma=None, lam=None):
+        """The geodesic regional term exists for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
+        self._no_metrics("refit_regional_geodesic")
 
     # -- the other minimum cuts (DESIGN 13c)
     CUT_SETS_INFO_KEYS = ("from_source", "to_sink", "ambiguous", "forward_passes", "forward_seeds", "backward_passes", "backward_seeds",
@@ -2122,6 +2233,17 @@ class EmbeddedLatticeGraph(object):
         """of the lattice part (``VoxelGraph.overlap_counts``)"""
         return self._inner.overlap_counts(reference, labels)
 
+    def geodesic_distance(self, seeds="fg", gamma=1.0, step=1.0, spacing=None, connectivity=None):
+        """of the lattice part (``VoxelGraph.geodesic_distance``), in the lattice's shape"""
+        return self._inner.geodesic_distance(seeds, gamma, step, spacing, connectivity)
+
+    def geodesic_info(self):
+        return self._inner.geodesic_info()
+
+    def refit_regional_geodesic(self, gamma=None, lam=None):
+        """of the lattice part (``VoxelGraph.refit_regional_geodesic``: ValueError, such a graph is built without the term)"""
+        return self._inner.refit_regional_geodesic(gamma, lam)
+
     def stats(self):
         return self._inner.stats()
 
@@ -2235,6 +2357,7 @@ class GCGraph(object):
         self.__tr = None  # merged explicit t-links (graph.h:416-425 applied call by call)
         self.__tdense = []  # (source, sink): whole t-link weight arrays, in call order (set_tweights_dense), while no per-node t-weight exists;
         #                     (_HistogramTerm, None): a histogram term (record_regional_histogram), fitted when the markers are known
+        #                     (_GeodesicTerm, None): a geodesic term (record_regional_geodesic), fitted when the markers are known
         self.__markers_recorded = False
         self.__flow_const = 0.0
         self.__graph = None
@@ -2299,6 +2422,35 @@ class GCGraph(object):
         if self.__graph is not None:
             raise NotImplementedError("medpy_amd: the graph is built already: VoxelGraph.refit_regional_histogram / update_tweights_binned change its t-links")
         self.__tdense.append((_HistogramTerm(image.reshape(self.__shape), nbins, lo, width, float(lam), float(eps)), None))
+
+    def record_regional_geodesic(self, gamma, lam, step=1.0, spacing=None, connectivity=None, image=None):
+        """The geodesic regional term (``energy_voxel.regional_geodesic``; medpy_amd/csrc/mgc_geo.h is its definition): with D_F and
+        D_B the geodesic distances of a voxel to the foreground and to the background markers (``VoxelGraph.geodesic_distance``
+        with ``gamma``, ``step``, ``spacing``, ``connectivity``) voxel p gets ``set_tweight(p, lam * D_B / (D_F + D_B),
+        lam * D_F / (D_F + D_B))`` -- all of ``lam`` to the side that alone is reached, half each where both distances are 0,
+        nothing where neither side is reached.  The term is FITTED WHEN THE GRAPH IS BUILT, on the markers known then, keeps its
+        place in call order among the dense t-link calls, and is computed on the device (mgc_add_tweights_geodesic);
+        ``VoxelGraph.refit_regional_geodesic`` fits it again after a stroke.  ``image`` (of the volume's size) becomes the feature
+        image of the graph; None: the boundary term's image.  It exists on graphs of the tile solver whose explicit t-links are
+        nothing but dense calls: NotImplementedError elsewhere, when the graph is built.  ValueError for a bad parameter or an
+        image of another size, before anything is recorded."""
+        for name, v in (("gamma", gamma), ("lam", lam), ("step", step)):
+            VoxelGraph._geo_number("record_regional_geodesic", name, v)
+        nd = len(self.__shape)
+        if connectivity is not None and connectivity not in (1, nd):
+            raise ValueError("record_regional_geodesic: connectivity must be 1 (face neighbours) or %d (the full neighbourhood), got %r" % (nd, connectivity))
+        if spacing is not None:
+            sp = numpy.asarray(spacing, dtype=numpy.float64)
+            if sp.shape not in ((), (nd,)) or not (numpy.isfinite(sp).all() and (sp > 0).all()):
+                raise ValueError("record_regional_geodesic: the spacing must be a finite positive scalar or %d such values, got %r" % (nd, spacing))
+        if image is not None:
+            image = numpy.asarray(image)
+            if image.size != self.__nodes:
+                raise ValueError("geodesic image holds {} values for {} nodes".format(image.size, self.__nodes))
+            image = image.reshape(self.__shape)
+        if self.__graph is not None:
+            raise NotImplementedError("medpy_amd: the graph is built already: VoxelGraph.refit_regional_geodesic / update_tweights_geodesic change its t-links")
+        self.__tdense.append((_GeodesicTerm(float(gamma), float(lam), float(step), spacing, connectivity, image), None))
 
     def __histogram_arrays(self, term):
         """the two per-voxel arrays of a histogram term, evaluated on the host on the markers known now"""
@@ -2440,6 +2592,9 @@ class GCGraph(object):
     def __merge_dense_tweights(self):
         """the recorded dense calls, merged on the host in call order (a per-node t-weight follows, or the graph goes to a solver
         that takes one merged vector); a histogram term among them is fitted to the markers known now"""
+        if any(isinstance(source, _GeodesicTerm) for source, _ in self.__tdense):
+            raise NotImplementedError("medpy_amd: the geodesic regional term is implemented for the voxel lattice solver (1-D..3-D volumes, "
+                                      "VoxelGraph) on graphs whose explicit t-links are nothing but dense calls: its distances are computed on the device")
         if any(sink is None for _, sink in self.__tdense) and self.__fg is None and self.__bg is None and not self.__markers_recorded:
             raise NotImplementedError("medpy_amd: a per-node t-weight behind a histogram regional term, before the markers are known: "
                                       "the term is fitted to the markers; set the markers first")
@@ -2507,6 +2662,17 @@ class GCGraph(object):
                     g._add_tweights(source, sink)
                     continue
                 term = source   # counted and expanded on the device, in its place in call order
+                if isinstance(term, _GeodesicTerm):
+                    if term.image is not None and not (self.__boundary is not None and _same_array(term.image, self.__boundary[1])):
+                        if feature is None or not _same_array(term.image, feature):
+                            g._set_feature_image(term.image)
+                            feature = term.image
+                    elif feature is not None:
+                        g._set_feature_image(None)
+                        feature = None
+                    g._add_tweights_geodesic(term.gamma, term.lam, term.step, term.spacing, term.connectivity)
+                    g._geo_params = (term.gamma, term.lam, term.step, term.spacing, term.connectivity)
+                    continue
                 own = self.__boundary is not None and _same_array(term.image, self.__boundary[1])
                 if not own and (feature is None or not _same_array(term.image, feature)):
                     g._set_feature_image(term.image)
