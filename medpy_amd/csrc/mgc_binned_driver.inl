@@ -1,12 +1,12 @@
 /*
  * mgc_binned_driver.inl -- the host side of the binned regional term: mgc_set_feature_image, mgc_marker_histograms,
- * mgc_add_tweights_binned and mgc_update_tweights_binned.  Included ONCE, by the last line of mgc_reach_driver.inl, which is
- * itself the last line of mgc_kernels.hip: the kernels of mgc_binned_ops.inl come in here, behind every other kernel of the
- * library, so that the kernels of the solve keep their places in the code object ("Headline check").
+ * mgc_add_tweights_binned and mgc_update_tweights_binned.  Included ONCE, at the end of mgc_kernels.hip behind
+ * mgc_reach_driver.inl: the kernels of mgc_binned_ops.inl come in here, behind the kernels of the solve, which keep their places
+ * in the code object ("Headline check").
  *
  * The two table calls leave the store of mgc_tweight_ops.inl exactly as mgc_add_tweights / mgc_update_tweights of the expanded
- * arrays would: they share mgc_tw_alloc, mgc_tw_attach, mgc_tw_flow_const and mgc_update_tlinks with those calls and differ in
- * the kernel that fills the planes.  Every check comes before the first write.
+ * arrays would: they go through mgc_tw_commit as those calls do and differ in the kernel that fills the planes.  Every check
+ * comes before the first write.
  */
 #include "mgc_binned_ops.inl"
 
@@ -16,6 +16,25 @@ static bool mgc_binned_image(mgc_handle h, const void** image, int* dtype)
     if (h->d_feat) { *image = h->d_feat; *dtype = h->feat_dtype; return true; }
     if (h->d_image) { *image = h->d_image; *dtype = h->img_dtype; return true; }
     return false;
+}
+
+/* A float image must be finite: checked on the device before the first write of a call.  MGC_OK (an integer image at once), or
+ * the refusal that names the lowest flat index of a value that is not; `must`: its last words, which differ from call to call. */
+static int mgc_float_image_check(mgc_handle h, const char* what, const void* image, int dtype, const char* must)
+{
+    if (dtype != MGC_F32 && dtype != MGC_F64) return MGC_OK;
+    unsigned long long first = MGC_BINNED_NONE;
+    const hipError_t e = mgc_first_offender(h, [&](unsigned long long* d_first) {
+        const int64_t wgs = ((h->nvox + 1) / 2 + 255) / 256;
+        const unsigned grid = (unsigned)(wgs < 4096 ? wgs : 4096);
+        if (dtype == MGC_F32) hipLaunchKernelGGL((k_binned_check<float>), dim3(grid), dim3(256), 0, h->stream, h->nvox, (const float*)image, d_first);
+        else hipLaunchKernelGGL((k_binned_check<double>), dim3(grid), dim3(256), 0, h->stream, h->nvox, (const double*)image, d_first);
+    }, &first);
+    MGC_HIP(h, e);
+    if (first == MGC_BINNED_NONE) return MGC_OK;
+    double v = 0.0;
+    MGC_HIP(h, mgc_fetch_value(image, dtype, (int64_t)first, &v));
+    return mgc_fail(h, MGC_ERR_INVALID, "%s: image[%lld] = %g: %s", what, (long long)first, v, must);
 }
 
 template <class T>
@@ -44,54 +63,22 @@ static int mgc_binned_tweights(mgc_handle h, const char* what, bool update, int6
     if (h->d_tr_in && !h->tw_store) return mgc_fail(h, MGC_ERR_STATE, "%s: the handle's explicit t-links came from mgc_set_tweights_merged (mgc_clear_tweights first)", what);
     MGC_HIP(h, hipSetDevice(h->device));
     MgcRange range_(what);
-    typedef std::chrono::steady_clock Clock;
-    auto ms_since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
-    auto t0 = Clock::now();
-    /* a float image must be finite: checked on the device before the first write */
-    if (dtype == MGC_F32 || dtype == MGC_F64) {
-        unsigned long long* const h_first = (unsigned long long*)(h->h_scalar + 7);
-        unsigned long long* const d_first = (unsigned long long*)(h->d_scalar + 7);
-        MGC_HIP(h, hipMemsetAsync(d_first, 0xff, sizeof(double), h->stream));
-        const int64_t wgs = ((h->nvox + 1) / 2 + 255) / 256;
-        const unsigned grid = (unsigned)(wgs < 4096 ? wgs : 4096);
-        if (dtype == MGC_F32) hipLaunchKernelGGL((k_binned_check<float>), dim3(grid), dim3(256), 0, h->stream, h->nvox, (const float*)image, d_first);
-        else hipLaunchKernelGGL((k_binned_check<double>), dim3(grid), dim3(256), 0, h->stream, h->nvox, (const double*)image, d_first);
-        MGC_HIP(h, hipGetLastError());
-        MGC_HIP(h, hipMemcpyAsync(h_first, d_first, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        MGC_HIP(h, hipStreamSynchronize(h->stream));
-        if (*h_first != MGC_BINNED_NONE) {
-            const int64_t id = (int64_t)*h_first;
-            double v = 0.0;
-            float vf = 0.f;
-            if (dtype == MGC_F32) { MGC_HIP(h, hipMemcpy(&vf, (const float*)image + id, sizeof(float), hipMemcpyDeviceToHost)); v = vf; }
-            else MGC_HIP(h, hipMemcpy(&v, (const double*)image + id, sizeof(double), hipMemcpyDeviceToHost));
-            return mgc_fail(h, MGC_ERR_INVALID, "%s: image[%lld] = %g: the feature image must be finite", what, (long long)id, v);
-        }
-    }
-    const double check_ms = ms_since(t0);
-    t0 = Clock::now();
-    /* what can fail for want of memory comes first: the two tables, and the store of a handle that has none */
-    double* d_tables = nullptr;
-    MGC_HIP(h, mgc_dmalloc((void**)&d_tables, (size_t)(2 * nbins) * sizeof(double)));
-    double* store = h->d_tr_in;
-    double* part = h->d_tw_part;
-    hipError_t e = hipSuccess;
-    if (!h->tw_store) e = mgc_tw_alloc(h, &store, &part);
-    if (e != hipSuccess) { (void)mgc_dfree(d_tables); MGC_HIP(h, e); }
-    auto give_back = [&]() {
-        (void)hipStreamSynchronize(h->stream);
-        (void)mgc_dfree(d_tables);
-        if (!h->tw_store) { (void)mgc_dfree(store); (void)mgc_dfree(part); }
-    };
-    unsigned long long* const d_changed = (unsigned long long*)(h->d_scalar + 6);
-    e = hipMemcpyAsync(d_tables, source_table, (size_t)nbins * sizeof(double), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_tables + nbins, sink_table, (size_t)nbins * sizeof(double), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess && update) e = hipMemsetAsync(d_changed, 0, sizeof(double), h->stream);
-    if (e == hipSuccess) {
+    auto t0 = std::chrono::steady_clock::now();
+    { const int rc = mgc_float_image_check(h, what, image, dtype, "the feature image must be finite"); if (rc) return rc; }
+    const double check_ms = mgc_ms_since(t0);
+    t0 = std::chrono::steady_clock::now();
+    /* what can fail for want of memory comes first: the two tables, then (mgc_tw_commit) the store of a handle that has none */
+    MgcBlocks pool;
+    double* const d_tables = (double*)pool.get((size_t)(2 * nbins) * sizeof(double));
+    MGC_HIP(h, pool.err);
+    MgcTwTimes ms;
+    ms.fill_ms = mgc_ms_since(t0);
+    const int rc = mgc_tw_commit(h, what, update ? MGC_TW_WARM : MGC_TW_COLD, pool, [&](double* store, double* share, unsigned long long* changed) {
+        hipError_t e = hipMemcpyAsync(d_tables, source_table, (size_t)nbins * sizeof(double), hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_tables + nbins, sink_table, (size_t)nbins * sizeof(double), hipMemcpyHostToDevice, h->stream);
+        if (e != hipSuccess) return e;
         const int64_t wgs = ((h->nvox + 1) / 2 + 255) / 256;
         const unsigned grid = (unsigned)(wgs < 8192 ? wgs : 8192);
-        double* const share = store + mgc_tw_share_at(h);
-        unsigned long long* const changed = update ? d_changed : nullptr;
         switch (dtype) {
         case MGC_U8: mgc_binned_expand<uint8_t>(h, grid, update, image, nbins, lo, width, d_tables, store, share, changed); break;
         case MGC_I8: mgc_binned_expand<int8_t>(h, grid, update, image, nbins, lo, width, d_tables, store, share, changed); break;
@@ -104,33 +91,12 @@ static int mgc_binned_tweights(mgc_handle h, const char* what, bool update, int6
         case MGC_F32: mgc_binned_expand<float>(h, grid, update, image, nbins, lo, width, d_tables, store, share, changed); break;
         default: mgc_binned_expand<double>(h, grid, update, image, nbins, lo, width, d_tables, store, share, changed); break;
         }
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && update) e = hipMemcpyAsync(h->h_scalar + 6, d_changed, sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    const double expand_ms = ms_since(t0);
-    t0 = Clock::now();
-    double total = 0.0;
-    if (e == hipSuccess) e = mgc_tw_flow_const(h, store, part, 0, nullptr, &total);
-    if (e != hipSuccess) { give_back(); MGC_HIP(h, e); }
-    const double flow_const_ms = ms_since(t0);
-    (void)mgc_dfree(d_tables); /* (the stream is quiet: the block goes back before the call returns) */
-    if (!h->tw_store) mgc_tw_attach(h, store, part);
-    h->flow_const_in = total;
-    if (!update) {
-        h->tw_info[0]++;
-        h->built = h->solved = false;
-        /* no error: the note says where the time of this call went (tools/gpu_histogram_term.py records it) */
-        (void)mgc_fail(h, MGC_OK, "%s: check_ms=%.3f expand_ms=%.3f flow_const_ms=%.3f", what, check_ms, expand_ms, flow_const_ms);
-        return MGC_OK;
-    }
-    h->tw_info[0] = 1; /* what clear + one mgc_add_tweights leave */
-    h->tw_info[1] = 0;
-    h->tw_info[2] = (int64_t)*(const unsigned long long*)(h->h_scalar + 6);
-    h->has_prev = false;
-    t0 = Clock::now();
-    { const int rc = mgc_update_tlinks(h); if (rc) return rc; }
-    (void)mgc_fail(h, MGC_OK, "%s: check_ms=%.3f expand_ms=%.3f flow_const_ms=%.3f fold_ms=%.3f", what, check_ms, expand_ms, flow_const_ms, ms_since(t0));
+        return hipGetLastError();
+    }, &ms);
+    if (rc) return rc;
+    /* no error: the note says where the time of this call went (tools/gpu_histogram_term.py records it) */
+    if (!update) (void)mgc_fail(h, MGC_OK, "%s: check_ms=%.3f expand_ms=%.3f flow_const_ms=%.3f", what, check_ms, ms.fill_ms, ms.flow_const_ms);
+    else (void)mgc_fail(h, MGC_OK, "%s: check_ms=%.3f expand_ms=%.3f flow_const_ms=%.3f fold_ms=%.3f", what, check_ms, ms.fill_ms, ms.flow_const_ms, ms.fold_ms);
     return MGC_OK;
 }
 
@@ -203,9 +169,7 @@ int mgc_marker_histograms(mgc_handle h, int64_t nbins, double lo, double width, 
     if (host[words - 1] != MGC_BINNED_NONE) {
         const int64_t id = (int64_t)host[words - 1];
         double v = 0.0;
-        float vf = 0.f;
-        if (dtype == MGC_F32) { MGC_HIP(h, hipMemcpy(&vf, (const float*)image + id, sizeof(float), hipMemcpyDeviceToHost)); v = vf; }
-        else MGC_HIP(h, hipMemcpy(&v, (const double*)image + id, sizeof(double), hipMemcpyDeviceToHost));
+        MGC_HIP(h, mgc_fetch_value(image, dtype, id, &v));
         return mgc_fail(h, MGC_ERR_INVALID, "mgc_marker_histograms: image[%lld] = %g under a marker: the feature image must be finite", (long long)id, v);
     }
     for (int64_t b = 0; b < nbins; ++b) { fg_hist[b] = (int64_t)host[(size_t)b]; bg_hist[b] = (int64_t)host[(size_t)(nbins + b)]; }
@@ -225,6 +189,3 @@ int mgc_update_tweights_binned(mgc_handle h, int64_t nbins, double lo, double wi
 }
 
 } /* extern "C" */
-
-/* (behind the kernels of this file as well: the histograms over every voxel, DESIGN 15 -- the last code of the library) */
-#include "mgc_label_hist_driver.inl"

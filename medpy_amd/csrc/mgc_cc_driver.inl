@@ -1,9 +1,9 @@
 /*
- * mgc_cc_driver.inl -- the host side of mgc_components and mgc_clean_labels.  Included ONCE, by the last line of
- * mgc_label_hist_driver.inl: the kernels of mgc_cc_ops.inl come in here, behind every other kernel of the library, so that the
+ * mgc_cc_driver.inl -- the host side of mgc_components and mgc_clean_labels.  Included ONCE, at the end of
+ * mgc_kernels.hip behind mgc_label_hist_driver.inl: the kernels of mgc_cc_ops.inl come in here, behind those, so that the
  * kernels before them keep their places in the code object ("Headline check").  Every check comes before the first write,
  * and a call leaves the handle as it was: it reads the labels, the label summaries and the marker planes, and every block it uses
- * comes from the pool and goes back before it returns (MgcReachBlocks).
+ * comes from the pool and goes back before it returns (MgcBlocks).
  */
 #include "mgc_cc_ops.inl"
 
@@ -26,7 +26,7 @@ struct MgcCcTable {
     uint8_t* flags = nullptr;
 };
 
-static void mgc_cc_alloc(mgc_handle h, MgcReachBlocks& pool, MgcCcPlanes& P)
+static void mgc_cc_alloc(mgc_handle h, MgcBlocks& pool, MgcCcPlanes& P)
 {
     const size_t n = (size_t)h->nvox;
     P.nseg = (h->nvox + MGC_CC_SEG - 1) / MGC_CC_SEG;
@@ -40,7 +40,7 @@ static void mgc_cc_alloc(mgc_handle h, MgcReachBlocks& pool, MgcCcPlanes& P)
 
 /* One labelling of `plane` (device, C order): afterwards P.parent holds the ids, T the first min(K, cap) rows, h_info the out8.
  * tsum: the label summaries when the plane is the current cut's labels and the read-out wrote them, else NULL. */
-static hipError_t mgc_cc_run(mgc_handle h, MgcReachBlocks& pool, const MgcCcPlanes& P, const uint8_t* plane, const uint8_t* tsum, int side, int full, int64_t cap, MgcCcTable& T,
+static hipError_t mgc_cc_run(mgc_handle h, MgcBlocks& pool, const MgcCcPlanes& P, const uint8_t* plane, const uint8_t* tsum, int side, int full, int64_t cap, MgcCcTable& T,
                              unsigned long long h_info[8])
 {
     const MgcLattice& L = h->L;
@@ -98,7 +98,7 @@ static int mgc_cc_check(mgc_handle h, const char* name, const uint8_t* labels)
 
 /* *plane: the device plane to label -- the labels of the current cut where they lie, or a caller's plane in a block of the call,
  * brought to 0 / 1 bytes; *tsum: the label summaries that go with it or NULL */
-static hipError_t mgc_cc_plane(mgc_handle h, MgcReachBlocks& pool, const uint8_t* labels, const uint8_t** plane, const uint8_t** tsum)
+static hipError_t mgc_cc_plane(mgc_handle h, MgcBlocks& pool, const uint8_t* labels, const uint8_t** plane, const uint8_t** tsum)
 {
     *tsum = nullptr;
     if (!labels) {
@@ -116,16 +116,6 @@ static hipError_t mgc_cc_plane(mgc_handle h, MgcReachBlocks& pool, const uint8_t
     return hipGetLastError();
 }
 
-/* the blocks go back (on a drained stream); an error becomes the handle's message under the entry point's name */
-static int mgc_cc_end(mgc_handle h, MgcReachBlocks& pool, hipError_t e, const char* name)
-{
-    (void)hipStreamSynchronize(h->stream);
-    pool.release();
-    if (e == hipSuccess) return MGC_OK;
-    (void)hipGetLastError();
-    return mgc_fail(h, e == hipErrorOutOfMemory ? MGC_ERR_OOM : MGC_ERR_HIP, "%s: %s", name, hipGetErrorString(e));
-}
-
 extern "C" {
 
 int mgc_components(mgc_handle h, const uint8_t* labels, int side, int full, int32_t* ids, int64_t cap, int64_t* first, int64_t* size, uint8_t* flags, int64_t* out8)
@@ -138,7 +128,7 @@ int mgc_components(mgc_handle h, const uint8_t* labels, int side, int full, int3
     if (cap > 0 && (!first || !size || !flags)) return mgc_fail(h, MGC_ERR_INVALID, "mgc_components: first / size / flags NULL with a capacity of %lld", (long long)cap);
     MGC_HIP(h, hipSetDevice(h->device));
     MgcRange range_("mgc_components");
-    MgcReachBlocks pool;
+    MgcBlocks pool;
     MgcCcPlanes P;
     MgcCcTable T;
     unsigned long long h_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -155,7 +145,7 @@ int mgc_components(mgc_handle h, const uint8_t* labels, int side, int full, int3
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     }
     if (e == hipSuccess && ids) e = mgc_staged_copy(h, P.parent, ids, (size_t)h->nvox * sizeof(int32_t), false);
-    const int rc = mgc_cc_end(h, pool, e, "mgc_components");
+    const int rc = mgc_blocks_end(h, pool, e, "mgc_components");
     if (rc != MGC_OK) return rc;
     if (out8)
         for (int k = 0; k < 8; ++k) out8[k] = (int64_t)h_info[k];
@@ -175,7 +165,7 @@ int mgc_clean_labels(mgc_handle h, const uint8_t* labels, const mgc_clean_rule* 
     if (cap < 0) return mgc_fail(h, MGC_ERR_INVALID, "mgc_clean_labels: the capacity of the list must not be negative, got %lld", (long long)cap);
     MGC_HIP(h, hipSetDevice(h->device));
     MgcRange range_("mgc_clean_labels");
-    MgcReachBlocks pool;
+    MgcBlocks pool;
     MgcCcPlanes P;
     int64_t res[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const uint8_t* plane = nullptr;
@@ -189,7 +179,7 @@ int mgc_clean_labels(mgc_handle h, const uint8_t* labels, const mgc_clean_rule* 
     hipError_t e = pool.err;
     if (e == hipSuccess) e = mgc_cc_plane(h, pool, labels, &plane, &tsum);
     /* step 1: the foreground components, the rule on the host, one keep byte per component back up */
-    MgcReachBlocks own; /* the table and the keep bytes of a step: back to the pool on a drained stream, after an error too */
+    MgcBlocks own; /* the table and the keep bytes of a step: back to the pool on a drained stream, after an error too */
     for (int step = 0; step < 2 && e == hipSuccess; ++step) {
         if (step == 1 && !rule->fill_holes) break;
         MgcCcTable T;
@@ -241,7 +231,7 @@ int mgc_clean_labels(mgc_handle h, const uint8_t* labels, const mgc_clean_rule* 
         res[6] = 1;
     }
     if (e == hipSuccess && out) e = mgc_staged_copy(h, d_out, out, (size_t)nvox, false);
-    const int rc = mgc_cc_end(h, pool, e, "mgc_clean_labels");
+    const int rc = mgc_blocks_end(h, pool, e, "mgc_clean_labels");
     if (rc != MGC_OK) return rc;
     if (out8)
         for (int k = 0; k < 8; ++k) out8[k] = res[k];
@@ -249,6 +239,3 @@ int mgc_clean_labels(mgc_handle h, const uint8_t* labels, const mgc_clean_rule* 
 }
 
 } /* extern "C" */
-
-/* (behind the kernels of this file as well: the distance transform and the surface metrics, DESIGN 17 -- the last code of the library) */
-#include "mgc_edt_driver.inl"

@@ -1,9 +1,9 @@
 /*
  * mgc_edt_driver.inl -- the host side of mgc_distance_transform, mgc_surface_distances and mgc_overlap_counts.  Included
- * ONCE, by the last line of mgc_cc_driver.inl: the kernels of mgc_edt_ops.inl come in here, behind every other kernel of the library,
+ * ONCE, at the end of mgc_kernels.hip behind mgc_cc_driver.inl: the kernels of mgc_edt_ops.inl come in here, behind those,
  * so that the kernels before them keep their places in the code object ("Headline check").  Every check comes before the
  * first write, and a call leaves the handle as it was: it reads the labels of the current cut or planes of the caller's, and every
- * block it uses comes from the pool and goes back before it returns (MgcReachBlocks, mgc_cc_end).  No field of the handle is new.
+ * block it uses comes from the pool and goes back before it returns (MgcBlocks, mgc_blocks_end).  No field of the handle is new.
  */
 #include "mgc_edt_ops.inl"
 
@@ -41,7 +41,7 @@ static bool mgc_edt_spacing(mgc_handle h, const double* spacing, double sp[3], i
 }
 
 /* the device plane of a call: the labels of the current cut where they lie, or a caller's plane in a block of the call */
-static hipError_t mgc_edt_plane(mgc_handle h, MgcReachBlocks& pool, const uint8_t* host, const uint8_t** plane)
+static hipError_t mgc_edt_plane(mgc_handle h, MgcBlocks& pool, const uint8_t* host, const uint8_t** plane)
 {
     if (!host) {
         *plane = h->d_labels;
@@ -54,7 +54,7 @@ static hipError_t mgc_edt_plane(mgc_handle h, MgcReachBlocks& pool, const uint8_
 }
 
 /* tot[0..3] = voxels of class tp, fp, fn, tn of p against q (q NULL: all zero); *off (or NULL): the scanned counts of p, nseg + 1 words */
-static hipError_t mgc_edt_count(mgc_handle h, MgcReachBlocks& pool, const uint8_t* p, const uint8_t* q, unsigned long long** off, unsigned long long tot[4])
+static hipError_t mgc_edt_count(mgc_handle h, MgcBlocks& pool, const uint8_t* p, const uint8_t* q, unsigned long long** off, unsigned long long tot[4])
 {
     const int64_t nseg = (h->nvox + MGC_EDT_COUNT_SEG - 1) / MGC_EDT_COUNT_SEG;
     unsigned long long* const cnt = (unsigned long long*)pool.get((size_t)(nseg + 1) * sizeof(unsigned long long));
@@ -74,7 +74,7 @@ static hipError_t mgc_edt_count(mgc_handle h, MgcReachBlocks& pool, const uint8_
 /* The transform of `plane` with the seeds of `side`, nseeds of them: *result is a plane of nvox doubles of the pool.  The last axis
  * from the bytes, then y and z where the volume has them (an axis of extent 1 adds fl(g + 0) = g: nothing to do); *long_lines grows
  * by the lines that were too long for a panel. */
-static hipError_t mgc_edt_transform(mgc_handle h, MgcReachBlocks& pool, const uint8_t* plane, int side, const double sp[3], int64_t nseeds, double** result, int64_t* long_lines)
+static hipError_t mgc_edt_transform(mgc_handle h, MgcBlocks& pool, const uint8_t* plane, int side, const double sp[3], int64_t nseeds, double** result, int64_t* long_lines)
 {
     const MgcLattice& L = h->L;
     const int64_t nvox = h->nvox;
@@ -123,7 +123,7 @@ int mgc_distance_transform(mgc_handle h, const uint8_t* plane, int side, const d
     if (!mgc_edt_spacing(h, spacing, sp, &bad)) return mgc_fail(h, MGC_ERR_INVALID, "mgc_distance_transform: spacing[%d] = %g: the spacing must be finite and positive", bad, spacing[bad]);
     MGC_HIP(h, hipSetDevice(h->device));
     MgcRange range_("mgc_distance_transform");
-    MgcReachBlocks pool;
+    MgcBlocks pool;
     const uint8_t* d_plane = nullptr;
     unsigned long long tot[4] = {0, 0, 0, 0};
     double* g = nullptr;
@@ -135,7 +135,7 @@ int mgc_distance_transform(mgc_handle h, const uint8_t* plane, int side, const d
         if (out_sq) e = mgc_edt_transform(h, pool, d_plane, side, sp, nseeds, &g, &long_lines);
     }
     if (e == hipSuccess && out_sq) e = mgc_staged_copy(h, g, out_sq, (size_t)h->nvox * sizeof(double), false);
-    const int rc = mgc_cc_end(h, pool, e, "mgc_distance_transform");
+    const int rc = mgc_blocks_end(h, pool, e, "mgc_distance_transform");
     if (rc != MGC_OK) return rc;
     if (out4) {
         out4[MGC_EDT_SEEDS] = nseeds;
@@ -158,7 +158,7 @@ int mgc_surface_distances(mgc_handle h, const uint8_t* a, const uint8_t* b, int 
     if (!mgc_edt_spacing(h, spacing, sp, &bad)) return mgc_fail(h, MGC_ERR_INVALID, "mgc_surface_distances: spacing[%d] = %g: the spacing must be finite and positive", bad, spacing[bad]);
     MGC_HIP(h, hipSetDevice(h->device));
     MgcRange range_("mgc_surface_distances");
-    MgcReachBlocks pool;
+    MgcBlocks pool;
     const MgcLattice& L = h->L;
     const int64_t nvox = h->nvox, nseg = (nvox + MGC_EDT_COUNT_SEG - 1) / MGC_EDT_COUNT_SEG;
     const unsigned g_vox = mgc_edt_grid((nvox + 255) / 256, 65536);
@@ -192,7 +192,7 @@ int mgc_surface_distances(mgc_handle h, const uint8_t* a, const uint8_t* b, int 
         }
         if (e == hipSuccess) e = mgc_staged_copy(h, d_out, sds_sq, (size_t)rows * sizeof(double), false);
     }
-    const int rc = mgc_cc_end(h, pool, e, "mgc_surface_distances");
+    const int rc = mgc_blocks_end(h, pool, e, "mgc_surface_distances");
     if (rc != MGC_OK) return rc;
     if (out8) {
         out8[MGC_SD_BORDER_A] = n_a;
@@ -213,20 +213,17 @@ int mgc_overlap_counts(mgc_handle h, const uint8_t* a, const uint8_t* b, int64_t
     if (!out4) return mgc_fail(h, MGC_ERR_INVALID, "mgc_overlap_counts: out4 NULL");
     MGC_HIP(h, hipSetDevice(h->device));
     MgcRange range_("mgc_overlap_counts");
-    MgcReachBlocks pool;
+    MgcBlocks pool;
     const uint8_t* d_a = nullptr;
     const uint8_t* d_b = nullptr;
     unsigned long long tot[4] = {0, 0, 0, 0};
     hipError_t e = mgc_edt_plane(h, pool, a, &d_a);
     if (e == hipSuccess) e = mgc_edt_plane(h, pool, b, &d_b);
     if (e == hipSuccess) e = mgc_edt_count(h, pool, d_a, d_b, nullptr, tot);
-    const int rc = mgc_cc_end(h, pool, e, "mgc_overlap_counts");
+    const int rc = mgc_blocks_end(h, pool, e, "mgc_overlap_counts");
     if (rc != MGC_OK) return rc;
     for (int k = 0; k < 4; ++k) out4[k] = (int64_t)tot[k];
     return MGC_OK;
 }
 
 } /* extern "C" */
-
-/* (behind the kernels of this file as well: the geodesic distance transform and its regional term, DESIGN 18 -- the last code of the library) */
-#include "mgc_geo_driver.inl"

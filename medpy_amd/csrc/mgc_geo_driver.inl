@@ -1,13 +1,12 @@
 /*
  * mgc_geo_driver.inl -- the host side of mgc_geodesic_distance, mgc_add_tweights_geodesic and mgc_update_tweights_geodesic.
- * Included ONCE, by the last line of mgc_edt_driver.inl: the kernels of mgc_geo_ops.inl come in here, behind every other kernel of
- * the library, so that the kernels before them keep their places in the code object ("Headline check").  Every check comes
- * before the first write.  mgc_geodesic_distance leaves the handle as it was: it reads the image and the marker planes, and every
- * block it uses comes from the pool and goes back before it returns (MgcReachBlocks, mgc_cc_end).  The two calls of the term leave
- * the t-link store exactly as mgc_add_tweights / mgc_update_tweights of the expanded arrays would: they share mgc_tw_alloc,
- * mgc_tw_attach, mgc_tw_flow_const and mgc_update_tlinks with those calls (as mgc_binned_tweights does) and differ in the kernel that
- * fills the planes; the warm form differs in one more thing, the label snapshot of mgc_labels_delta, which it keeps as
- * mgc_edit_tweights does.  No field of the handle is new.
+ * Included ONCE, as the last of the drivers at the end of mgc_kernels.hip: the kernels of mgc_geo_ops.inl come in here, behind every
+ * other kernel of the library, so that the kernels before them keep their places in the code object ("Headline check").
+ * Every check comes before the first write.  mgc_geodesic_distance leaves the handle as it was: it reads the image and the marker
+ * planes, and every block it uses comes from the pool and goes back before it returns (MgcBlocks, mgc_blocks_end).  The two calls of
+ * the term leave the t-link store exactly as mgc_add_tweights / mgc_update_tweights of the expanded arrays would: they go through
+ * mgc_tw_commit as those calls do (and mgc_binned_tweights) and differ in what fills the planes; the warm form differs in one more
+ * thing, the label snapshot of mgc_labels_delta, which it keeps as mgc_edit_tweights does.  No field of the handle is new.
  */
 #include "mgc_geo_ops.inl"
 
@@ -34,26 +33,7 @@ static int mgc_geo_image(mgc_handle h, const char* name, double gamma, const voi
     if (gamma == 0.0) return MGC_OK;
     if (!mgc_binned_image(h, image, dtype))
         return mgc_fail(h, MGC_ERR_STATE, "%s: gamma = %g > 0 and the handle holds no feature image (mgc_set_feature_image) and no boundary image (mgc_set_boundary)", name, gamma);
-    if (*dtype != MGC_F32 && *dtype != MGC_F64) return MGC_OK;
-    unsigned long long* const h_first = (unsigned long long*)(h->h_scalar + 7);
-    unsigned long long* const d_first = (unsigned long long*)(h->d_scalar + 7);
-    MGC_HIP(h, hipMemsetAsync(d_first, 0xff, sizeof(double), h->stream));
-    const int64_t wgs = ((h->nvox + 1) / 2 + 255) / 256;
-    const unsigned grid = (unsigned)(wgs < 4096 ? wgs : 4096);
-    if (*dtype == MGC_F32) hipLaunchKernelGGL((k_binned_check<float>), dim3(grid), dim3(256), 0, h->stream, h->nvox, (const float*)*image, d_first);
-    else hipLaunchKernelGGL((k_binned_check<double>), dim3(grid), dim3(256), 0, h->stream, h->nvox, (const double*)*image, d_first);
-    MGC_HIP(h, hipGetLastError());
-    MGC_HIP(h, hipMemcpyAsync(h_first, d_first, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    MGC_HIP(h, hipStreamSynchronize(h->stream));
-    if (*h_first != MGC_BINNED_NONE) {
-        const int64_t id = (int64_t)*h_first;
-        double v = 0.0;
-        float vf = 0.f;
-        if (*dtype == MGC_F32) { MGC_HIP(h, hipMemcpy(&vf, (const float*)*image + id, sizeof(float), hipMemcpyDeviceToHost)); v = vf; }
-        else MGC_HIP(h, hipMemcpy(&v, (const double*)*image + id, sizeof(double), hipMemcpyDeviceToHost));
-        return mgc_fail(h, MGC_ERR_INVALID, "%s: image[%lld] = %g: the image must be finite", name, (long long)id, v);
-    }
-    return MGC_OK;
+    return mgc_float_image_check(h, name, *image, *dtype, "the image must be finite");
 }
 
 /* One transform: *result is a plane of nvox doubles of the pool (C order), info the eight slots of out8.  seeds: a byte plane on the
@@ -61,7 +41,7 @@ static int mgc_geo_image(mgc_handle h, const char* name, double gamma, const voi
  * host looks at the length of the next list after every launch and stops at the round that woke nobody.  After round r every voxel
  * whose best path has at most r arcs holds its value, and a path visits a voxel once: more than nvox + 1 rounds cannot happen, and
  * *stuck says so instead of spinning. */
-static hipError_t mgc_geo_transform(mgc_handle h, MgcReachBlocks& pool, const uint8_t* seeds, int full, double gamma, const MgcGeoSteps& S, const void* image, int dtype,
+static hipError_t mgc_geo_transform(mgc_handle h, MgcBlocks& pool, const uint8_t* seeds, int full, double gamma, const MgcGeoSteps& S, const void* image, int dtype,
                                     double** result, unsigned long long info[8], bool* stuck)
 {
     const MgcLattice& L = h->L;
@@ -132,14 +112,12 @@ static int mgc_geo_tweights(mgc_handle h, const char* what, bool update, int ful
     if (h->d_tr_in && !h->tw_store) return mgc_fail(h, MGC_ERR_STATE, "%s: the handle's explicit t-links came from mgc_set_tweights_merged (mgc_clear_tweights first)", what);
     MGC_HIP(h, hipSetDevice(h->device));
     MgcRange range_(what);
-    typedef std::chrono::steady_clock Clock;
-    auto ms_since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
-    auto t0 = Clock::now();
+    auto t0 = std::chrono::steady_clock::now();
     const void* image = nullptr;
     int dtype = 0;
     { const int rc = mgc_geo_image(h, what, gamma, &image, &dtype); if (rc) return rc; }
     /* the two planes live for this call only; nothing of the handle has changed while they are computed */
-    MgcReachBlocks pool;
+    MgcBlocks pool;
     double* dist[2] = {nullptr, nullptr};
     unsigned long long info[2][8];
     bool stuck = false;
@@ -147,68 +125,32 @@ static int mgc_geo_tweights(mgc_handle h, const char* what, bool update, int ful
     for (int k = 0; k < 2 && e == hipSuccess && !stuck; ++k)
         e = mgc_geo_transform(h, pool, (const uint8_t*)(k == 0 ? h->d_fg : h->d_bg), full, gamma, S, image, dtype, &dist[k], info[k], &stuck);
     if (e != hipSuccess || stuck) {
-        const int rc = mgc_cc_end(h, pool, e, what);
+        const int rc = mgc_blocks_end(h, pool, e, what);
         return rc != MGC_OK ? rc : mgc_fail(h, MGC_ERR_HIP, "%s: the transform did not reach its fixpoint within %lld rounds", what, (long long)(h->nvox + 1));
     }
-    const double transform_ms = ms_since(t0);
-    t0 = Clock::now();
-    /* what can fail for want of memory comes first: the label snapshot of a finished cut, the store of a handle that has none */
-    if (update && h->solved && !h->d_labels_prev) {
-        (void)hipStreamSynchronize(h->stream);
-        const int rc = mgc_alloc(h, &h->d_labels_prev, h->nvox);
-        if (rc) return rc;
-    }
-    double* store = h->d_tr_in;
-    double* part = h->d_tw_part;
-    if (!h->tw_store) e = mgc_tw_alloc(h, &store, &part);
-    if (e != hipSuccess) return mgc_cc_end(h, pool, e, what);
-    auto give_back = [&]() {
-        (void)hipStreamSynchronize(h->stream);
-        if (!h->tw_store) { (void)mgc_dfree(store); (void)mgc_dfree(part); }
-    };
-    unsigned long long* const d_changed = (unsigned long long*)(h->d_scalar + 6);
-    if (update) e = hipMemsetAsync(d_changed, 0, sizeof(double), h->stream);
-    if (e == hipSuccess) {
-        double* const share = store + mgc_tw_share_at(h);
-        if (update) mgc_geo_expand<true>(h, dist[0], dist[1], lam, store, share, d_changed);
+    const double transform_ms = mgc_ms_since(t0);
+    t0 = std::chrono::steady_clock::now();
+    /* What can fail for want of memory comes first: the label snapshot of a finished cut, then (mgc_tw_commit) the store of a handle
+       that has none.  The refit follows a stroke, and the caller asks which voxels the round changed: unlike mgc_update_tweights the
+       warm form keeps the snapshot of mgc_labels_delta, the way mgc_edit_tweights does. */
+    if (update) { const int rc = mgc_snapshot_reserve(h); if (rc) return rc; }
+    MgcTwTimes ms;
+    ms.fill_ms = mgc_ms_since(t0);
+    const int rc = mgc_tw_commit(h, what, update ? MGC_TW_WARM_KEEP : MGC_TW_COLD, pool, [&](double* store, double* share, unsigned long long* changed) {
+        if (update) mgc_geo_expand<true>(h, dist[0], dist[1], lam, store, share, changed);
         else mgc_geo_expand<false>(h, dist[0], dist[1], lam, store, share, nullptr);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && update) e = hipMemcpyAsync(h->h_scalar + 6, d_changed, sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    const double expand_ms = ms_since(t0);
-    t0 = Clock::now();
-    double total = 0.0;
-    if (e == hipSuccess) e = mgc_tw_flow_const(h, store, part, 0, nullptr, &total);
-    if (e != hipSuccess) { give_back(); return mgc_cc_end(h, pool, e, what); }
-    const double flow_const_ms = ms_since(t0);
-    (void)mgc_cc_end(h, pool, hipSuccess, what); /* (the stream is quiet: the planes go back before the call returns) */
-    if (!h->tw_store) mgc_tw_attach(h, store, part);
-    h->flow_const_in = total;
+        return hipGetLastError();
+    }, &ms);
+    if (rc) return rc;
     const long long rounds[2] = {(long long)info[0][MGC_GEO_ROUNDS], (long long)info[1][MGC_GEO_ROUNDS]};
     const long long visits[2] = {(long long)info[0][MGC_GEO_VISITS], (long long)info[1][MGC_GEO_VISITS]};
-    if (!update) {
-        h->tw_info[0]++;
-        h->built = h->solved = false;
-        /* no error: the note says where the time of this call went (tools/gpu_geodesic.py records it) */
-        (void)mgc_fail(h, MGC_OK, "%s: transform_ms=%.3f expand_ms=%.3f flow_const_ms=%.3f rounds_fg=%lld rounds_bg=%lld visits_fg=%lld visits_bg=%lld", what, transform_ms, expand_ms,
-                       flow_const_ms, rounds[0], rounds[1], visits[0], visits[1]);
-        return MGC_OK;
-    }
-    h->tw_info[0] = 1; /* what clear + one mgc_add_tweights leave */
-    h->tw_info[1] = 0;
-    h->tw_info[2] = (int64_t)*(const unsigned long long*)(h->h_scalar + 6);
-    /* The refit follows a stroke, and the caller asks which voxels the round changed: unlike mgc_update_tweights the warm form keeps
-       the label snapshot of mgc_labels_delta the way mgc_edit_tweights does -- the labels of a finished cut change hands; after an
-       edit that the next solve has yet to see, the snapshot that edit took stays. */
-    if (h->solved) {
-        std::swap(h->d_labels, h->d_labels_prev);
-        h->has_prev = true;
-    }
-    t0 = Clock::now();
-    { const int rc = mgc_update_tlinks(h); if (rc) return rc; }
-    (void)mgc_fail(h, MGC_OK, "%s: transform_ms=%.3f expand_ms=%.3f flow_const_ms=%.3f fold_ms=%.3f rounds_fg=%lld rounds_bg=%lld visits_fg=%lld visits_bg=%lld", what, transform_ms,
-                   expand_ms, flow_const_ms, ms_since(t0), rounds[0], rounds[1], visits[0], visits[1]);
+    /* no error: the note says where the time of this call went (tools/gpu_geodesic.py records it) */
+    if (!update)
+        (void)mgc_fail(h, MGC_OK, "%s: transform_ms=%.3f expand_ms=%.3f flow_const_ms=%.3f rounds_fg=%lld rounds_bg=%lld visits_fg=%lld visits_bg=%lld", what, transform_ms, ms.fill_ms,
+                       ms.flow_const_ms, rounds[0], rounds[1], visits[0], visits[1]);
+    else
+        (void)mgc_fail(h, MGC_OK, "%s: transform_ms=%.3f expand_ms=%.3f flow_const_ms=%.3f fold_ms=%.3f rounds_fg=%lld rounds_bg=%lld visits_fg=%lld visits_bg=%lld", what, transform_ms,
+                       ms.fill_ms, ms.flow_const_ms, ms.fold_ms, rounds[0], rounds[1], visits[0], visits[1]);
     return MGC_OK;
 }
 
@@ -228,7 +170,7 @@ int mgc_geodesic_distance(mgc_handle h, const uint8_t* seeds, int source, int fu
     const void* image = nullptr;
     int dtype = 0;
     { const int rc = mgc_geo_image(h, "mgc_geodesic_distance", gamma, &image, &dtype); if (rc) return rc; }
-    MgcReachBlocks pool;
+    MgcBlocks pool;
     const uint8_t* d_seeds = (const uint8_t*)(source == 1 ? h->d_fg : h->d_bg);
     hipError_t e = hipSuccess;
     if (source == 0) e = mgc_edt_plane(h, pool, seeds, &d_seeds);
@@ -237,7 +179,7 @@ int mgc_geodesic_distance(mgc_handle h, const uint8_t* seeds, int source, int fu
     bool stuck = false;
     if (e == hipSuccess) e = mgc_geo_transform(h, pool, d_seeds, full, gamma, S, image, dtype, &plane, info, &stuck);
     if (e == hipSuccess && !stuck && out) e = mgc_staged_copy(h, plane, out, (size_t)h->nvox * sizeof(double), false);
-    const int rc = mgc_cc_end(h, pool, e, "mgc_geodesic_distance");
+    const int rc = mgc_blocks_end(h, pool, e, "mgc_geodesic_distance");
     if (rc != MGC_OK) return rc;
     if (stuck) return mgc_fail(h, MGC_ERR_HIP, "mgc_geodesic_distance: the transform did not reach its fixpoint within %lld rounds", (long long)(h->nvox + 1));
     if (out8)

@@ -2730,6 +2730,24 @@ struct MgcRange { /* scope guard */
 };
 static std::string g_create_error;
 
+/* The eight doubles of mgc_graph::d_scalar and of its pinned mirror h_scalar, by what they hold.  A slot with two names serves two
+ * calls that have nothing to do with each other: each waits for the stream and reads its word before it returns, so neither finds
+ * the other's.  mgc_build, mgc_update_tlinks, the read-out of a solve, mgc_validate and the cut sets copy all MGC_S_COUNT at once. */
+enum MgcScalar {
+    MGC_S_BUILD_CONST = 0, /* k_build / k_update_tlinks: the built t-links' part of the flow constant */
+    MGC_S_CUT = 1,         /* the read-out of a solve: the capacity of the cut the labels define */
+    MGC_S_SINK_FLOW = 2,   /* mgc_validate: the flow into the sink */
+    MGC_S_VALIDATE_CUT = 3, /* mgc_validate: the capacity of the cut, read out again */
+    MGC_S_CUT_SOURCE = 4,  /* mgc_cut_sets, mgc_cut_sets_tol: the cut around the source side */
+    MGC_S_TW_CONST = 5,    /* mgc_tw_flow_const: the flow constant of the t-link store */
+    MGC_S_CUT_SINK = 5,    /* ... and mgc_cut_sets_tol: the cut around the sink side */
+    MGC_S_CHANGED = 6,     /* the calls that fill or edit the t-link store: voxels whose t-link changed (an integer word) */
+    MGC_S_EDGE = 6,        /* ... and mgc_get_edge: the residual it reads */
+    MGC_S_OFFENDER = 7,    /* mgc_first_offender: the lowest offender of a check (an integer word) */
+    MGC_S_DELTA_TOTAL = 7, /* ... and mgc_labels_delta: how many labels changed (an integer word) */
+    MGC_S_COUNT = 8
+};
+
 struct mgc_graph {
     int device = 0;
     int ndim = 0;
@@ -3009,6 +3027,45 @@ static int mgc_alloc(mgc_handle h, T** p, int64_t count)
     MGC_HIP(h, mgc_dmalloc((void**)p, (size_t)count * sizeof(T)));
     h->device_bytes += count * (int64_t)sizeof(T);
     return MGC_OK;
+}
+
+/* the pool blocks that live for one call: get() after a failed get() allocates nothing, err is the first error */
+struct MgcBlocks {
+    std::vector<void*> held;
+    hipError_t err = hipSuccess;
+    void* get(size_t bytes)
+    {
+        void* p = nullptr;
+        if (err == hipSuccess) err = mgc_dmalloc(&p, bytes);
+        if (p) held.push_back(p);
+        return p;
+    }
+    void release()
+    {
+        for (void* p : held) (void)mgc_dfree(p);
+        held.clear();
+    }
+    ~MgcBlocks() { release(); }
+};
+
+/* a HIP error becomes the handle's message under the entry point's name */
+static int mgc_hip_fail(mgc_handle h, const char* name, hipError_t e)
+{
+    (void)hipGetLastError();
+    return mgc_fail(h, e == hipErrorOutOfMemory ? MGC_ERR_OOM : MGC_ERR_HIP, "%s: %s", name, hipGetErrorString(e));
+}
+
+/* the blocks of a call go back (on a drained stream); MGC_OK, or the error as mgc_hip_fail words it */
+static int mgc_blocks_end(mgc_handle h, MgcBlocks& pool, hipError_t e, const char* name)
+{
+    (void)hipStreamSynchronize(h->stream);
+    pool.release();
+    return e == hipSuccess ? MGC_OK : mgc_hip_fail(h, name, e);
+}
+
+static double mgc_ms_since(std::chrono::steady_clock::time_point t0)
+{
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 /* the counter block as the host sees it: slot c = its plain word + its shard words (a slot is used one way or the other) */
@@ -3851,10 +3908,10 @@ static int mgc_create_impl(int ndim, const int64_t* shape, int connectivity, int
     if ((rc = mgc_alloc(h, &h->d_tsum, nt))) return rc;
     if ((rc = mgc_alloc(h, &h->d_part, nt > 4096 ? nt : (int64_t)4096))) return rc;
     if ((rc = mgc_alloc(h, &h->d_part2, (int64_t)256))) return rc;
-    if ((rc = mgc_alloc(h, &h->d_scalar, (int64_t)8))) return rc;
+    if ((rc = mgc_alloc(h, &h->d_scalar, (int64_t)MGC_S_COUNT))) return rc;
     if ((rc = mgc_alloc(h, &h->d_labels, n))) return rc;
     MGC_HIP(h, hipHostMalloc((void**)&h->h_count, MGC_NCOUNT * (1 + MGC_NSHARD) * sizeof(int32_t), hipHostMallocDefault));
-    MGC_HIP(h, hipHostMalloc((void**)&h->h_scalar, 8 * sizeof(double), hipHostMallocDefault));
+    MGC_HIP(h, hipHostMalloc((void**)&h->h_scalar, MGC_S_COUNT * sizeof(double), hipHostMallocDefault));
     MGC_HIP(h, hipHostMalloc((void**)&h->h_look, (MGC_NCOUNT * (1 + MGC_NSHARD) + 1) * sizeof(int32_t), hipHostMallocMapped | hipHostMallocCoherent));
     memset(h->h_look, 0, (MGC_NCOUNT * (1 + MGC_NSHARD) + 1) * sizeof(int32_t));
     MGC_HIP(h, hipHostGetDevicePointer((void**)&h->d_look, h->h_look, 0));
@@ -4532,6 +4589,22 @@ static int mgc_update_check(mgc_handle h, const char* what)
     return MGC_OK;
 }
 
+/* The label snapshot of mgc_labels_delta, for the warm calls that keep it.  reserve: what can fail for want of memory, before the
+ * first write.  take: the labels of a finished solve are put aside by the two buffers changing hands -- nothing reads d_labels
+ * between an update of the t-links and the next read-out, which writes every voxel of it; a call that finds the handle unsolved
+ * (an edit the next solve has yet to see) leaves the snapshot that edit took. */
+static int mgc_snapshot_reserve(mgc_handle h)
+{
+    return h->solved && !h->d_labels_prev ? mgc_alloc(h, &h->d_labels_prev, h->nvox) : MGC_OK;
+}
+
+static void mgc_snapshot_take(mgc_handle h)
+{
+    if (!h->solved) return;
+    std::swap(h->d_labels, h->d_labels_prev);
+    h->has_prev = true;
+}
+
 static int mgc_edit_overrides(mgc_handle h);
 
 static int mgc_update_tlinks(mgc_handle h)
@@ -4552,10 +4625,10 @@ static int mgc_update_tlinks(mgc_handle h)
     if (L.ndir == 6) hipLaunchKernelGGL(k_update_tlinks<false>, dim3(grid), dim3(MGC_TV), 0, h->stream, L, A);
     else hipLaunchKernelGGL(k_update_tlinks<true>, dim3(grid), dim3(MGC_TV), 0, h->stream, L, A);
     MGC_HIP(h, hipGetLastError());
-    mgc_sum_partials(h, (int64_t)L.ntiles, h->d_scalar);
+    mgc_sum_partials(h, (int64_t)L.ntiles, h->d_scalar + MGC_S_BUILD_CONST);
     MGC_HIP(h, hipGetLastError());
     MGC_HIP(h, hipEventRecord(h->ev[1], h->stream));
-    MGC_HIP(h, hipMemcpyAsync(h->h_scalar, h->d_scalar, 8 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    MGC_HIP(h, hipMemcpyAsync(h->h_scalar, h->d_scalar, MGC_S_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     MGC_HIP(h, hipMemcpyAsync(h->h_count, L.count, MGC_NCOUNT * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     MGC_HIP(h, hipStreamSynchronize(h->stream));
     if (L.ndir == 6) h->sink_tiles = h->h_count[MGC_CNT_SINK_TILES];
@@ -4563,7 +4636,7 @@ static int mgc_update_tlinks(mgc_handle h)
     float ms = 0.f;
     MGC_HIP(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
     h->stats.update_ms = ms;
-    h->flow_const = h->h_scalar[0] + (h->d_tr_in ? h->flow_const_in : 0.0); /* (bit for bit what mgc_build computes from these inputs) */
+    h->flow_const = h->h_scalar[MGC_S_BUILD_CONST] + (h->d_tr_in ? h->flow_const_in : 0.0); /* (bit for bit what mgc_build computes from these inputs) */
     h->all_residual = false; /* saturated n-links: the first global relabel of the next solve runs as passes from scratch */
     h->solved = false;
     h->labels_valid = false;
@@ -4682,7 +4755,7 @@ int mgc_edit_markers(mgc_handle h, int64_t n, const int64_t* ids, const uint8_t*
     MGC_HIP(h, hipSetDevice(h->device));
     MgcRange range_("mgc_edit_markers");
     /* what can fail for want of memory comes first */
-    if (h->solved && !h->d_labels_prev) { const int rc = mgc_alloc(h, &h->d_labels_prev, h->nvox); if (rc) return rc; }
+    { const int rc = mgc_snapshot_reserve(h); if (rc) return rc; }
     void* d_list = nullptr; void* own = nullptr;
     const size_t ops_at = (size_t)n * sizeof(int64_t);
     { const int rc = mgc_call_scratch(h, 0, ops_at + (size_t)n, &d_list, &own); if (rc) return rc; }
@@ -4690,13 +4763,7 @@ int mgc_edit_markers(mgc_handle h, int64_t n, const int64_t* ids, const uint8_t*
     if (set_fg) rc = mgc_zero_plane(h, &h->d_fg);
     if (!rc && set_bg) rc = mgc_zero_plane(h, &h->d_bg);
     if (rc) { (void)mgc_dfree(own); return rc; }
-    if (h->solved) {
-        /* The labels of the finished solve: what mgc_labels_delta holds the next solve against.  Nothing reads d_labels between an
-         * update of the t-links and the next read-out, which writes every voxel of it -- so the copy aside is the two buffers changing
-         * hands, not 2 x nvox bytes through HBM.  Further edits before that solve find the handle unsolved and keep the copy. */
-        std::swap(h->d_labels, h->d_labels_prev);
-        h->has_prev = true;
-    }
+    mgc_snapshot_take(h);
     hipError_t e = hipMemcpyAsync(d_list, ids, ops_at, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync((char*)d_list + ops_at, ops, (size_t)n, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipEventRecord(h->ev[2], h->stream);
@@ -4749,7 +4816,7 @@ int mgc_labels_delta(mgc_handle h, int64_t cap, int64_t* ids, int64_t* n)
     MGC_HIP(h, hipEventRecord(h->ev[2], h->stream));
     MGC_HIP(h, mgc_labels_delta_launch(h->stream, h->d_labels, h->d_labels_prev, h->nvox, d_off, 0, nullptr));
     MGC_HIP(h, hipEventRecord(h->ev[3], h->stream));
-    unsigned long long* const h_total = (unsigned long long*)(h->h_scalar + 7);
+    unsigned long long* const h_total = (unsigned long long*)(h->h_scalar + MGC_S_DELTA_TOTAL);
     MGC_HIP(h, hipMemcpyAsync(h_total, d_off + nseg, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
     MGC_HIP(h, hipStreamSynchronize(h->stream));
     MGC_HIP(h, hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
@@ -4785,12 +4852,12 @@ int mgc_validate(mgc_handle h, mgc_validation* out)
     const int grid = L.ntiles < h->grid_cap * 4 ? L.ntiles : h->grid_cap * 4;
     hipLaunchKernelGGL(k_validate, dim3(grid), dim3(MGC_TV), 0, h->stream, L, h->build_args, (const double*)h->d_tr0, h->d_part, d_out);
     MGC_HIP(h, hipGetLastError());
-    mgc_sum_partials(h, (int64_t)L.ntiles, h->d_scalar + 2);
+    mgc_sum_partials(h, (int64_t)L.ntiles, h->d_scalar + MGC_S_SINK_FLOW);
     /* the capacity of the cut the current labels define (the labels are read from the distance labels, as k_labels does) */
-    { const int rc = mgc_launch_readout(h, 3, nullptr); if (rc) return rc; }
+    { const int rc = mgc_launch_readout(h, MGC_S_VALIDATE_CUT, nullptr); if (rc) return rc; }
     MgcValidateOut ho;
     MGC_HIP(h, hipMemcpyAsync(&ho, d_out, sizeof(ho), hipMemcpyDeviceToHost, h->stream));
-    MGC_HIP(h, hipMemcpyAsync(h->h_scalar, h->d_scalar, 8 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    MGC_HIP(h, hipMemcpyAsync(h->h_scalar, h->d_scalar, MGC_S_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     MGC_HIP(h, hipStreamSynchronize(h->stream));
     h->labels_on_host = false;
     out->voxels = (int64_t)ho.cnt[0]; out->negative_values = (int64_t)ho.cnt[1]; out->active_excess = (int64_t)ho.cnt[2];
@@ -4798,8 +4865,8 @@ int mgc_validate(mgc_handle h, mgc_validation* out)
     out->pair_violations = (int64_t)ho.cnt[5]; out->node_violations = (int64_t)ho.cnt[6]; out->pending_outbox = (int64_t)ho.cnt[7];
     memcpy(&out->max_pair_error, &ho.max_pair_bits, sizeof(double));
     memcpy(&out->max_node_error, &ho.max_node_bits, sizeof(double));
-    out->flow_into_sink = h->h_scalar[2];
-    out->cut_capacity = h->h_scalar[3];
+    out->flow_into_sink = h->h_scalar[MGC_S_SINK_FLOW];
+    out->cut_capacity = h->h_scalar[MGC_S_VALIDATE_CUT];
     out->flow_constant = h->flow_const;
     out->sink_capacity_used = ho.sink_cap_used;
     return MGC_OK;
@@ -4887,14 +4954,14 @@ static void mgc_dense_drop(mgc_handle h)
     }
 }
 
-static void mgc_dense_launch(mgc_handle h, bool f32, bool check, const void* there, const void* back, const int* o, double* base_d, int64_t stride_d,
+/* first != NULL: the check, which leaves the first offender there; else the accumulation into the planes */
+static void mgc_dense_launch(mgc_handle h, bool f32, unsigned long long* first, const void* there, const void* back, const int* o, double* base_d, int64_t stride_d,
                              double* base_r, int64_t stride_r)
 {
     const MgcLattice& L = h->L;
-    if (check) {
+    if (first) {
         const int64_t rows = L.dz * L.dy;
         const int grid = (int)std::min<int64_t>((rows + 3) / 4, 4096);
-        unsigned long long* const first = (unsigned long long*)(h->d_scalar + 7);
         if (f32) hipLaunchKernelGGL((k_dense_check<float>), dim3(grid), dim3(256), 0, h->stream, L, (const float*)there, (const float*)back, o[0], o[1], o[2], first);
         else hipLaunchKernelGGL((k_dense_check<double>), dim3(grid), dim3(256), 0, h->stream, L, (const double*)there, (const double*)back, o[0], o[1], o[2], first);
     } else {
@@ -4905,6 +4972,36 @@ static void mgc_dense_launch(mgc_handle h, bool f32, bool check, const void* the
         else hipLaunchKernelGGL((k_dense_accumulate<double>), dim3(grid), dim3(MGC_TV), 0, h->stream, L, (const double*)there, (const double*)back, o[0], o[1], o[2],
                                 base_d, stride_d, base_r, stride_r);
     }
+}
+
+/* A check on the device before the first write: launch(first) enqueues a kernel that leaves the lowest offender in the word
+ * `first` (atomicMin), which starts as all ones -- the NONE of every check.  Waits for the stream; *word is what the kernel left. */
+extern "C++" {
+template <class Launch>
+static hipError_t mgc_first_offender(mgc_handle h, Launch launch, unsigned long long* word)
+{
+    unsigned long long* const h_first = (unsigned long long*)(h->h_scalar + MGC_S_OFFENDER);
+    unsigned long long* const d_first = (unsigned long long*)(h->d_scalar + MGC_S_OFFENDER);
+    hipError_t e = hipMemsetAsync(d_first, 0xff, sizeof(double), h->stream);
+    if (e == hipSuccess) {
+        launch(d_first);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(h_first, d_first, sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess) *word = *h_first;
+    return e;
+}
+} /* extern "C++" */
+
+/* element id of a device array of MGC_F32 or MGC_F64, for the refusal that names an offender */
+static hipError_t mgc_fetch_value(const void* array, int dtype, int64_t id, double* v)
+{
+    if (dtype != MGC_F32) return hipMemcpy(v, (const double*)array + id, sizeof(double), hipMemcpyDeviceToHost);
+    float vf = 0.f;
+    const hipError_t e = hipMemcpy(&vf, (const float*)array + id, sizeof(float), hipMemcpyDeviceToHost);
+    *v = vf;
+    return e;
 }
 
 int mgc_add_nweights(mgc_handle h, const int* offset, const void* there, const void* back, int dtype)
@@ -4927,7 +5024,6 @@ int mgc_add_nweights(mgc_handle h, const int* offset, const void* there, const v
     const size_t bytes = (size_t)h->nvox * (dtype == MGC_F32 ? sizeof(float) : sizeof(double));
     const int64_t plane = (int64_t)L.ntiles * MGC_TV;
     typedef std::chrono::steady_clock Clock;
-    auto ms_since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
     /* the arrays go up into blocks of the pool that are given back before the call returns */
     void* tmp[2] = {nullptr, nullptr};
     double* fresh[3] = {nullptr, nullptr, nullptr}; /* what this call allocates for the store: given back if it does not go through */
@@ -4942,26 +5038,18 @@ int mgc_add_nweights(mgc_handle h, const int* offset, const void* there, const v
     if (e == hipSuccess) e = mgc_staged_copy(h, tmp[0], const_cast<void*>(there), bytes, true);
     if (e == hipSuccess && back) e = mgc_staged_copy(h, tmp[1], const_cast<void*>(back), bytes, true);
     if (e != hipSuccess) { release(); MGC_HIP(h, e); }
-    const double upload_ms = ms_since(t0);
+    const double upload_ms = mgc_ms_since(t0);
     /* the check, before the first write to the store */
     t0 = Clock::now();
-    unsigned long long* const h_first = (unsigned long long*)(h->h_scalar + 7);
-    e = hipMemsetAsync(h->d_scalar + 7, 0xff, sizeof(double), h->stream);
-    if (e == hipSuccess) {
-        mgc_dense_launch(h, dtype == MGC_F32, true, tmp[0], tmp[1], o, nullptr, 0, nullptr, 0);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(h_first, h->d_scalar + 7, sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    unsigned long long first = MGC_DENSE_NONE;
+    e = mgc_first_offender(h, [&](unsigned long long* d_first) { mgc_dense_launch(h, dtype == MGC_F32, d_first, tmp[0], tmp[1], o, nullptr, 0, nullptr, 0); }, &first);
     if (e != hipSuccess) { release(); MGC_HIP(h, e); }
-    const double check_ms = ms_since(t0);
-    if (*h_first != MGC_DENSE_NONE) {
-        const int which = (int)(*h_first & 1ull);
-        const int64_t id = (int64_t)(*h_first >> 1);
+    const double check_ms = mgc_ms_since(t0);
+    if (first != MGC_DENSE_NONE) {
+        const int which = (int)(first & 1ull);
+        const int64_t id = (int64_t)(first >> 1);
         double v = 0.0;
-        float vf = 0.f;
-        if (dtype == MGC_F32) { e = hipMemcpy(&vf, (const float*)tmp[which] + id, sizeof(float), hipMemcpyDeviceToHost); v = vf; }
-        else e = hipMemcpy(&v, (const double*)tmp[which] + id, sizeof(double), hipMemcpyDeviceToHost);
+        e = mgc_fetch_value(tmp[which], dtype, id, &v);
         release();
         MGC_HIP(h, e);
         return mgc_fail(h, MGC_ERR_INVALID, "mgc_add_nweights: %s[%lld] = %g: capacities must be finite and >= 0", which ? "back" : "there", (long long)id, v);
@@ -4984,11 +5072,11 @@ int mgc_add_nweights(mgc_handle h, const int* offset, const void* there, const v
         stride[k] = MGC_TV;
     }
     if (e != hipSuccess) { release(); MGC_HIP(h, e); }
-    mgc_dense_launch(h, dtype == MGC_F32, false, tmp[0], tmp[1], o, base[0], stride[0], base[1], stride[1]);
+    mgc_dense_launch(h, dtype == MGC_F32, nullptr, tmp[0], tmp[1], o, base[0], stride[0], base[1], stride[1]);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) { release(); MGC_HIP(h, e); }
-    const double accumulate_ms = ms_since(t0);
+    const double accumulate_ms = mgc_ms_since(t0);
     if (fresh[0]) { h->d_dense = fresh[0]; h->device_bytes += plane * L.ndir * (int64_t)sizeof(double); fresh[0] = nullptr; }
     for (int k = 0; k < 2; ++k) {
         if (fresh[1 + k]) { h->dense_extra[dir[k]].push_back(fresh[1 + k]); h->device_bytes += plane * (int64_t)sizeof(double); fresh[1 + k] = nullptr; }
@@ -5097,7 +5185,7 @@ int mgc_edit_nweights(mgc_handle h, int64_t n, const int64_t* i, const int64_t* 
     MGC_HIP(h, hipSetDevice(h->device));
     MgcRange range_("mgc_edit_nweights");
     /* what can fail for want of memory comes first */
-    if (h->solved && !h->d_labels_prev) { const int rc = mgc_alloc(h, &h->d_labels_prev, h->nvox); if (rc) return rc; }
+    { const int rc = mgc_snapshot_reserve(h); if (rc) return rc; }
     float fill_ms = 0.f, fold_ms = 0.f;
     if (!L.cap0) {
         /* an image-determined graph: its capacities as built are written out once.  The fill evaluates them through
@@ -5120,10 +5208,7 @@ int mgc_edit_nweights(mgc_handle h, int64_t n, const int64_t* i, const int64_t* 
         L.cap0 = fresh;
         h->device_bytes += count * (int64_t)sizeof(double);
     }
-    if (h->solved) { /* the snapshot rule of mgc_edit_markers: the finished solve's labels are put aside by the two buffers changing hands */
-        std::swap(h->d_labels, h->d_labels_prev);
-        h->has_prev = true;
-    }
+    mgc_snapshot_take(h);
     for (int64_t k = 0; k < n; ++k) {
         const double a = cap[k], b = rev ? rev[k] : cap[k];
         if (i[k] < j[k]) h->nw_over[{i[k], j[k]}] = {a, b};
@@ -5218,77 +5303,117 @@ static hipError_t mgc_tw_flow_const(mgc_handle h, double* store, double* part, i
     hipLaunchKernelGGL(k_tw_partials, dim3((unsigned)(wgs < 8192 ? wgs : 8192)), dim3(256), 0, h->stream, (const double*)(store + mgc_tw_share_at(h)), h->nvox, nsegs, d_segs, part);
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(MGC_TV), 0, h->stream, (const double*)part, all, part + all);
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(h->h_scalar + 5, part + all, sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h->h_scalar + MGC_S_TW_CONST, part + all, sizeof(double), hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e == hipSuccess) *total = h->h_scalar[5];
+    if (e == hipSuccess) *total = h->h_scalar[MGC_S_TW_CONST];
     return e;
 }
 
-/* The caller's two arrays go up into blocks of the pool (tmp[0], tmp[1]: the caller gives them back) and are checked there.
- * MGC_OK, or the refusal with the blocks given back already. */
-static int mgc_tw_upload_checked(mgc_handle h, const char* what, const void* source, const void* sink, int dtype, void** tmp, double* upload_ms, double* check_ms)
+/* the phase times of mgc_tw_commit, for the caller's note */
+struct MgcTwTimes { double fill_ms = 0.0, flow_const_ms = 0.0, fold_ms = 0.0; };
+
+/* cold: mgc_add_tweights*, the next mgc_build sees the store.  Warm: mgc_update_tweights*, folded into the built graph -- the label
+ * snapshot of mgc_labels_delta is dropped, or (KEEP) kept as mgc_edit_tweights keeps it */
+enum MgcTwForm { MGC_TW_COLD, MGC_TW_WARM, MGC_TW_WARM_KEEP };
+
+/* The one path of the calls that fill the whole store (mgc_add_tweights and mgc_update_tweights, their _binned and their _geodesic
+ * forms), from the point where the call's checks are through and what the fill reads lies on the device, in `pool`.  A handle without
+ * a store gets a fresh one; fill(store, share, changed) enqueues what writes the two planes and returns its first error (changed: the
+ * counter of a warm form, cleared; NULL on the cold form); the flow constant follows and the blocks of the call go back on a drained
+ * stream.  Only then does the handle change: the store is attached; the cold form counts the call and asks for a rebuild; a warm
+ * form reports what clear + one mgc_add_tweights leave, settles the snapshot and folds the new t-links in (mgc_update_tlinks).  A
+ * HIP error gives a fresh store back, and the handle is as it was.
+ * ms != NULL: the caller's note tells the phases apart, so the stream is drained behind the fill as well (ms == NULL: the flow
+ * constant is enqueued right behind it).  fill_ms comes in as what the caller has spent on the inputs of the fill already. */
+extern "C++" {
+template <class Fill>
+static int mgc_tw_commit(mgc_handle h, const char* what, MgcTwForm form, MgcBlocks& pool, Fill fill, MgcTwTimes* ms)
 {
     typedef std::chrono::steady_clock Clock;
-    auto ms_since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
+    const bool warm = form != MGC_TW_COLD, fresh = !h->tw_store;
+    auto t0 = Clock::now();
+    double* store = h->d_tr_in;
+    double* part = h->d_tw_part;
+    hipError_t e = fresh ? mgc_tw_alloc(h, &store, &part) : hipSuccess;
+    if (e != hipSuccess) return mgc_blocks_end(h, pool, e, what);
+    unsigned long long* const d_changed = warm ? (unsigned long long*)(h->d_scalar + MGC_S_CHANGED) : nullptr;
+    const unsigned long long* const h_changed = (const unsigned long long*)(h->h_scalar + MGC_S_CHANGED);
+    if (warm) e = hipMemsetAsync(d_changed, 0, sizeof(double), h->stream);
+    if (e == hipSuccess) e = fill(store, store + mgc_tw_share_at(h), d_changed);
+    if (e == hipSuccess && warm) e = hipMemcpyAsync(h->h_scalar + MGC_S_CHANGED, d_changed, sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess && ms) e = hipStreamSynchronize(h->stream);
+    if (ms) ms->fill_ms += mgc_ms_since(t0);
+    t0 = Clock::now();
+    double total = 0.0;
+    if (e == hipSuccess) e = mgc_tw_flow_const(h, store, part, 0, nullptr, &total);
+    if (ms) ms->flow_const_ms = mgc_ms_since(t0);
+    const int rc = mgc_blocks_end(h, pool, e, what);
+    if (rc) {
+        if (fresh) { (void)mgc_dfree(store); (void)mgc_dfree(part); }
+        return rc;
+    }
+    if (fresh) mgc_tw_attach(h, store, part);
+    h->flow_const_in = total;
+    if (!warm) {
+        h->tw_info[0]++;
+        h->built = h->solved = false;
+        return MGC_OK;
+    }
+    h->tw_info[0] = 1; /* what clear + one mgc_add_tweights leave */
+    h->tw_info[1] = 0;
+    h->tw_info[2] = (int64_t)*h_changed;
+    if (form == MGC_TW_WARM_KEEP) mgc_snapshot_take(h);
+    else h->has_prev = false;
+    t0 = Clock::now();
+    const int rc2 = mgc_update_tlinks(h);
+    if (ms) ms->fold_ms = mgc_ms_since(t0);
+    return rc2;
+}
+} /* extern "C++" */
+
+/* The caller's two arrays go up into blocks of the pool (tmp[0], tmp[1]) and are checked there.  MGC_OK, or the refusal with the
+ * blocks given back already. */
+static int mgc_tw_upload_checked(mgc_handle h, const char* what, const void* source, const void* sink, int dtype, MgcBlocks& pool, void** tmp, double* upload_ms,
+                                 double* check_ms)
+{
+    typedef std::chrono::steady_clock Clock;
     const bool f32 = dtype == MGC_F32;
     const size_t bytes = (size_t)h->nvox * (f32 ? sizeof(float) : sizeof(double));
-    tmp[0] = tmp[1] = nullptr;
-    auto release = [&]() {
-        (void)hipStreamSynchronize(h->stream);
-        for (int k = 0; k < 2; ++k) { if (tmp[k]) (void)mgc_dfree(tmp[k]); tmp[k] = nullptr; }
-    };
     auto t0 = Clock::now();
-    hipError_t e = mgc_dmalloc(&tmp[0], bytes);
-    if (e == hipSuccess) e = mgc_dmalloc(&tmp[1], bytes);
+    tmp[0] = pool.get(bytes);
+    tmp[1] = pool.get(bytes);
+    hipError_t e = pool.err;
     if (e == hipSuccess) e = mgc_staged_copy(h, tmp[0], const_cast<void*>(source), bytes, true);
     if (e == hipSuccess) e = mgc_staged_copy(h, tmp[1], const_cast<void*>(sink), bytes, true);
-    if (e != hipSuccess) { release(); MGC_HIP(h, e); }
-    *upload_ms = ms_since(t0);
+    if (e != hipSuccess) return mgc_blocks_end(h, pool, e, what);
+    *upload_ms = mgc_ms_since(t0);
     t0 = Clock::now();
-    unsigned long long* const h_first = (unsigned long long*)(h->h_scalar + 7);
-    unsigned long long* const d_first = (unsigned long long*)(h->d_scalar + 7);
-    e = hipMemsetAsync(d_first, 0xff, sizeof(double), h->stream);
-    if (e == hipSuccess) {
+    unsigned long long first = MGC_TW_NONE;
+    e = mgc_first_offender(h, [&](unsigned long long* d_first) {
         const int64_t wgs = ((h->nvox + 1) / 2 + 255) / 256;
         const unsigned grid = (unsigned)(wgs < 4096 ? wgs : 4096);
         if (f32) hipLaunchKernelGGL((k_tw_check<float>), dim3(grid), dim3(256), 0, h->stream, h->nvox, (const float*)tmp[0], (const float*)tmp[1], d_first);
         else hipLaunchKernelGGL((k_tw_check<double>), dim3(grid), dim3(256), 0, h->stream, h->nvox, (const double*)tmp[0], (const double*)tmp[1], d_first);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(h_first, d_first, sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) { release(); MGC_HIP(h, e); }
-    *check_ms = ms_since(t0);
-    if (*h_first != MGC_TW_NONE) {
-        const int which = (int)(*h_first & 1ull);
-        const int64_t id = (int64_t)(*h_first >> 1);
-        double v = 0.0;
-        float vf = 0.f;
-        if (f32) { e = hipMemcpy(&vf, (const float*)tmp[which] + id, sizeof(float), hipMemcpyDeviceToHost); v = vf; }
-        else e = hipMemcpy(&v, (const double*)tmp[which] + id, sizeof(double), hipMemcpyDeviceToHost);
-        release();
-        MGC_HIP(h, e);
-        return mgc_fail(h, MGC_ERR_INVALID, "%s: %s[%lld] = %g: t-link weights must be finite", what, which ? "sink" : "source", (long long)id, v);
-    }
-    return MGC_OK;
+    }, &first);
+    if (e != hipSuccess) return mgc_blocks_end(h, pool, e, what);
+    *check_ms = mgc_ms_since(t0);
+    if (first == MGC_TW_NONE) return MGC_OK;
+    const int which = (int)(first & 1ull);
+    const int64_t id = (int64_t)(first >> 1);
+    double v = 0.0;
+    e = mgc_fetch_value(tmp[which], dtype, id, &v);
+    const int rc = mgc_blocks_end(h, pool, e, what);
+    return rc ? rc : mgc_fail(h, MGC_ERR_INVALID, "%s: %s[%lld] = %g: t-link weights must be finite", what, which ? "sink" : "source", (long long)id, v);
 }
 
-/* k_tw_merge of checked arrays into `store`, then its flow constant from every segment.  Waits for the stream. */
-static hipError_t mgc_tw_merge(mgc_handle h, int dtype, void* const* tmp, double* store, double* part, bool fresh, bool count, double* total, int64_t* changed)
+/* the fill of the arrays pair: k_tw_merge of checked arrays.  changed != NULL: the warm form, on top of a zero t-link and a zero share */
+static hipError_t mgc_tw_merge(mgc_handle h, int dtype, void* const* tmp, double* store, double* share, unsigned long long* changed)
 {
-    unsigned long long* const d_changed = (unsigned long long*)(h->d_scalar + 6);
-    hipError_t e = count ? hipMemsetAsync(d_changed, 0, sizeof(double), h->stream) : hipSuccess;
-    if (e != hipSuccess) return e;
     const int64_t wgs = ((h->nvox + 1) / 2 + 255) / 256;
     const unsigned grid = (unsigned)(wgs < 8192 ? wgs : 8192);
-    double* const share = store + mgc_tw_share_at(h);
-    if (dtype == MGC_F32) hipLaunchKernelGGL((k_tw_merge<float>), dim3(grid), dim3(256), 0, h->stream, h->nvox, (const float*)tmp[0], (const float*)tmp[1], store, share, fresh ? 1 : 0, count ? d_changed : nullptr);
-    else hipLaunchKernelGGL((k_tw_merge<double>), dim3(grid), dim3(256), 0, h->stream, h->nvox, (const double*)tmp[0], (const double*)tmp[1], store, share, fresh ? 1 : 0, count ? d_changed : nullptr);
-    e = hipGetLastError();
-    if (e == hipSuccess && count) e = hipMemcpyAsync(h->h_scalar + 6, d_changed, sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = mgc_tw_flow_const(h, store, part, 0, nullptr, total);
-    if (e == hipSuccess && count) *changed = (int64_t)*(const unsigned long long*)(h->h_scalar + 6);
-    return e;
+    if (dtype == MGC_F32) hipLaunchKernelGGL((k_tw_merge<float>), dim3(grid), dim3(256), 0, h->stream, h->nvox, (const float*)tmp[0], (const float*)tmp[1], store, share, changed ? 1 : 0, changed);
+    else hipLaunchKernelGGL((k_tw_merge<double>), dim3(grid), dim3(256), 0, h->stream, h->nvox, (const double*)tmp[0], (const double*)tmp[1], store, share, changed ? 1 : 0, changed);
+    return hipGetLastError();
 }
 
 static int mgc_tw_args(mgc_handle h, const char* what, const void* source, const void* sink, int dtype)
@@ -5299,37 +5424,29 @@ static int mgc_tw_args(mgc_handle h, const char* what, const void* source, const
     return MGC_OK;
 }
 
+/* mgc_add_tweights (update false) and mgc_update_tweights (update true) behind their checks */
+static int mgc_tw_arrays(mgc_handle h, const char* what, bool update, const void* source, const void* sink, int dtype)
+{
+    MGC_HIP(h, hipSetDevice(h->device));
+    MgcRange range_(what);
+    MgcBlocks pool;
+    void* tmp[2];
+    double upload_ms = 0.0, check_ms = 0.0;
+    { const int rc = mgc_tw_upload_checked(h, what, source, sink, dtype, pool, tmp, &upload_ms, &check_ms); if (rc) return rc; }
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = mgc_tw_commit(h, what, update ? MGC_TW_WARM : MGC_TW_COLD, pool,
+                                 [&](double* store, double* share, unsigned long long* changed) { return mgc_tw_merge(h, dtype, tmp, store, share, changed); }, nullptr);
+    /* no error: the note says where the time of the cold call went (tools/gpu_dense_tweights.py records it); the warm one leaves none */
+    if (rc == MGC_OK && !update) (void)mgc_fail(h, MGC_OK, "%s: upload_ms=%.3f check_ms=%.3f accumulate_ms=%.3f", what, upload_ms, check_ms, mgc_ms_since(t0));
+    return rc;
+}
+
 int mgc_add_tweights(mgc_handle h, const void* source, const void* sink, int dtype)
 {
     if (!h) return MGC_ERR_INVALID;
     if (h->nranks > 1) return mgc_fail(h, MGC_ERR_UNSUPPORTED, "mgc_add_tweights: not on a slab of a multi-GPU volume");
     { const int rc = mgc_tw_args(h, "mgc_add_tweights", source, sink, dtype); if (rc) return rc; }
-    MGC_HIP(h, hipSetDevice(h->device));
-    typedef std::chrono::steady_clock Clock;
-    void* tmp[2];
-    double upload_ms = 0.0, check_ms = 0.0;
-    { const int rc = mgc_tw_upload_checked(h, "mgc_add_tweights", source, sink, dtype, tmp, &upload_ms, &check_ms); if (rc) return rc; }
-    const auto t0 = Clock::now();
-    double* store = h->d_tr_in;
-    double* part = h->d_tw_part;
-    hipError_t e = hipSuccess;
-    if (!h->tw_store) e = mgc_tw_alloc(h, &store, &part);
-    double total = 0.0;
-    if (e == hipSuccess) {
-        e = mgc_tw_merge(h, dtype, tmp, store, part, false, false, &total, nullptr);
-        if (e != hipSuccess && !h->tw_store) { (void)hipStreamSynchronize(h->stream); (void)mgc_dfree(store); (void)mgc_dfree(part); }
-    }
-    (void)hipStreamSynchronize(h->stream);
-    for (void* p : tmp) (void)mgc_dfree(p); /* the blocks go back before the call returns */
-    MGC_HIP(h, e);
-    const double accumulate_ms = std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
-    if (!h->tw_store) mgc_tw_attach(h, store, part);
-    h->flow_const_in = total;
-    h->tw_info[0]++;
-    h->built = h->solved = false;
-    /* no error: the note says where the time of this call went (tools/gpu_dense_tweights.py records it) */
-    (void)mgc_fail(h, MGC_OK, "mgc_add_tweights: upload_ms=%.3f check_ms=%.3f accumulate_ms=%.3f", upload_ms, check_ms, accumulate_ms);
-    return MGC_OK;
+    return mgc_tw_arrays(h, "mgc_add_tweights", false, source, sink, dtype);
 }
 
 int mgc_clear_tweights(mgc_handle h)
@@ -5347,31 +5464,7 @@ int mgc_update_tweights(mgc_handle h, const void* source, const void* sink, int 
     if (!h) return MGC_ERR_INVALID;
     { const int rc = mgc_update_check(h, "mgc_update_tweights"); if (rc) return rc; }
     { const int rc = mgc_tw_args(h, "mgc_update_tweights", source, sink, dtype); if (rc) return rc; }
-    MGC_HIP(h, hipSetDevice(h->device));
-    MgcRange range_("mgc_update_tweights");
-    void* tmp[2];
-    double upload_ms = 0.0, check_ms = 0.0;
-    { const int rc = mgc_tw_upload_checked(h, "mgc_update_tweights", source, sink, dtype, tmp, &upload_ms, &check_ms); if (rc) return rc; }
-    double* store = h->d_tr_in;
-    double* part = h->d_tw_part;
-    hipError_t e = hipSuccess;
-    if (!h->tw_store) e = mgc_tw_alloc(h, &store, &part);
-    double total = 0.0;
-    int64_t changed = 0;
-    if (e == hipSuccess) {
-        e = mgc_tw_merge(h, dtype, tmp, store, part, true, true, &total, &changed);
-        if (e != hipSuccess && !h->tw_store) { (void)hipStreamSynchronize(h->stream); (void)mgc_dfree(store); (void)mgc_dfree(part); }
-    }
-    (void)hipStreamSynchronize(h->stream);
-    for (void* p : tmp) (void)mgc_dfree(p);
-    MGC_HIP(h, e);
-    if (!h->tw_store) mgc_tw_attach(h, store, part);
-    h->flow_const_in = total;
-    h->tw_info[0] = 1; /* what clear + one mgc_add_tweights leave */
-    h->tw_info[1] = 0;
-    h->tw_info[2] = changed;
-    h->has_prev = false;
-    return mgc_update_tlinks(h);
+    return mgc_tw_arrays(h, "mgc_update_tweights", true, source, sink, dtype);
 }
 
 int mgc_edit_tweights(mgc_handle h, int64_t n, const int64_t* ids, const double* source, const double* sink)
@@ -5395,7 +5488,7 @@ int mgc_edit_tweights(mgc_handle h, int64_t n, const int64_t* ids, const double*
     MGC_HIP(h, hipSetDevice(h->device));
     MgcRange range_("mgc_edit_tweights");
     /* what can fail for want of memory comes first */
-    if (h->solved && !h->d_labels_prev) { const int rc = mgc_alloc(h, &h->d_labels_prev, h->nvox); if (rc) return rc; }
+    { const int rc = mgc_snapshot_reserve(h); if (rc) return rc; }
     const size_t list_bytes = (size_t)n * sizeof(int64_t), seg_bytes = segs.size() * sizeof(int64_t);
     void* d_list = nullptr; void* own = nullptr;
     { const int rc = mgc_call_scratch(h, 0, 3 * list_bytes + seg_bytes, &d_list, &own); if (rc) return rc; }
@@ -5405,12 +5498,9 @@ int mgc_edit_tweights(mgc_handle h, int64_t n, const int64_t* ids, const double*
         if (e != hipSuccess) { (void)mgc_dfree(own); MGC_HIP(h, e); }
         mgc_tw_attach(h, store, part);
     }
-    if (h->solved) { /* the labels of the finished solve change hands, as in mgc_edit_markers */
-        std::swap(h->d_labels, h->d_labels_prev);
-        h->has_prev = true;
-    }
+    mgc_snapshot_take(h);
     char* const base = (char*)d_list;
-    unsigned long long* const d_changed = (unsigned long long*)(h->d_scalar + 6);
+    unsigned long long* const d_changed = (unsigned long long*)(h->d_scalar + MGC_S_CHANGED);
     double* const share = h->d_tr_in + mgc_tw_share_at(h);
     hipError_t e = hipMemcpyAsync(base, ids, list_bytes, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(base + list_bytes, source, list_bytes, hipMemcpyHostToDevice, h->stream);
@@ -5424,14 +5514,14 @@ int mgc_edit_tweights(mgc_handle h, int64_t n, const int64_t* ids, const double*
                            (const double*)(base + list_bytes), (const double*)(base + 2 * list_bytes), h->d_tr_in, share, d_changed);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(h->h_scalar + 6, d_changed, sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h->h_scalar + MGC_S_CHANGED, d_changed, sizeof(double), hipMemcpyDeviceToHost, h->stream);
     double total = 0.0;
     if (e == hipSuccess) e = mgc_tw_flow_const(h, h->d_tr_in, h->d_tw_part, (int64_t)segs.size(), (const int64_t*)(base + 3 * list_bytes), &total);
     if (e == hipSuccess) e = hipEventRecord(h->ev[3], h->stream);
     if (e != hipSuccess) { (void)hipStreamSynchronize(h->stream); (void)mgc_dfree(own); MGC_HIP(h, e); }
     h->flow_const_in = total;
     h->tw_info[1] = n;
-    h->tw_info[2] = (int64_t)*(const unsigned long long*)(h->h_scalar + 6);
+    h->tw_info[2] = (int64_t)*(const unsigned long long*)(h->h_scalar + MGC_S_CHANGED);
     int rc = mgc_update_tlinks(h); /* (waits for the stream: the list is consumed) */
     (void)mgc_dfree(own);
     if (rc) return rc;
@@ -5514,7 +5604,7 @@ int mgc_build(mgc_handle h)
     if (L.ndir == 6) mgc_launch_build<false>(A.term, bgrid, h->stream, L, A);
     else mgc_launch_build<true>(A.term, bgrid, h->stream, L, A);
     MGC_HIP(h, hipGetLastError());
-    mgc_sum_partials(h, (int64_t)L.ntiles, h->d_scalar);
+    mgc_sum_partials(h, (int64_t)L.ntiles, h->d_scalar + MGC_S_BUILD_CONST);
     MGC_HIP(h, hipGetLastError());
     /* the order is fixed: the boundary term's weight (k_build), then the dense store, then the batch of mgc_add_edges, then --
      * behind everything else of the build, below -- the capacities set by mgc_edit_nweights */
@@ -5552,7 +5642,7 @@ int mgc_build(mgc_handle h)
         }
     }
     MGC_HIP(h, hipEventRecord(h->ev[1], h->stream));
-    MGC_HIP(h, hipMemcpyAsync(h->h_scalar, h->d_scalar, 8 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    MGC_HIP(h, hipMemcpyAsync(h->h_scalar, h->d_scalar, MGC_S_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     MGC_HIP(h, hipMemcpyAsync(h->h_count, L.count, MGC_NCOUNT * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     MGC_HIP(h, hipStreamSynchronize(h->stream));
     /* every n-link of the volume residual (and nothing added on top that the mask refresh could have changed): the first
@@ -5568,7 +5658,7 @@ int mgc_build(mgc_handle h)
     float ms = 0.f;
     MGC_HIP(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
     h->stats.build_ms = ms;
-    h->flow_const = h->h_scalar[0] + (h->d_tr_in ? h->flow_const_in : 0.0);
+    h->flow_const = h->h_scalar[MGC_S_BUILD_CONST] + (h->d_tr_in ? h->flow_const_in : 0.0);
     /* the explicit edges stay with the handle: a rebuild (new markers, another sigma) applies them again; mgc_add_edges
      * after a build replaces them (one batch per build) */
     h->edges_applied = h->n_edges != 0;
@@ -5628,7 +5718,7 @@ int mgc_update_boundary(mgc_handle h, int term, const void* image, int dtype, do
     MGC_HIP(h, hipSetDevice(h->device));
     MgcRange range_("mgc_update_boundary");
     /* what can fail for want of memory comes first */
-    if (h->solved && !h->d_labels_prev) { const int rc = mgc_alloc(h, &h->d_labels_prev, h->nvox); if (rc) return rc; }
+    { const int rc = mgc_snapshot_reserve(h); if (rc) return rc; }
     const size_t bytes = (size_t)h->nvox * es;
     void* d_new = nullptr;
     if (image) { /* next to the old one, which the fold still reads */
@@ -5636,10 +5726,7 @@ int mgc_update_boundary(mgc_handle h, int term, const void* image, int dtype, do
         const hipError_t e = mgc_staged_copy(h, d_new, const_cast<void*>(image), bytes, true);
         if (e != hipSuccess) { (void)mgc_dfree(d_new); MGC_HIP(h, e); }
     }
-    if (h->solved) { /* the snapshot rule of mgc_edit_markers: the finished solve's labels are put aside by the two buffers changing hands */
-        std::swap(h->d_labels, h->d_labels_prev);
-        h->has_prev = true;
-    }
+    mgc_snapshot_take(h);
     const MgcBuildArgs A0 = h->build_args;
     void* const d_old = h->d_image;
     const size_t old_cap = h->buf_cap[(const void*)&h->d_image];
@@ -5794,8 +5881,8 @@ int mgc_maxflow(mgc_handle h, double* flow)
             return mgc_fail(h, MGC_ERR_NOT_CONVERGED, "solver did not converge within %d global relabels", h->params.max_outer);
         }
         /* read-out: labels, then the capacity of the cut they define */
-        { const int rc2 = mgc_launch_readout(h, 1, h->ev[1]); if (rc2) return rc2; }
-        MGC_HIP(h, hipMemcpyAsync(h->h_scalar, h->d_scalar, 8 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        { const int rc2 = mgc_launch_readout(h, MGC_S_CUT, h->ev[1]); if (rc2) return rc2; }
+        MGC_HIP(h, hipMemcpyAsync(h->h_scalar, h->d_scalar, MGC_S_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         MGC_HIP(h, hipStreamSynchronize(h->stream));
         float ms = 0.f;
         MGC_HIP(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
@@ -5817,7 +5904,7 @@ int mgc_maxflow(mgc_handle h, double* flow)
         h->stats.relabel_tiles = st.relabel_tiles;
         h->stats.global_relabels = st.outer;
         h->stats.phases = st.phases;
-        h->flow = h->flow_const + h->h_scalar[1];
+        h->flow = h->flow_const + h->h_scalar[MGC_S_CUT];
         h->solved = true;
         h->converged = true;
         h->labels_on_host = false;
@@ -5833,8 +5920,8 @@ int mgc_finish(mgc_handle h, double* flow_partial)
     MGC_HIP(h, hipSetDevice(h->device));
     mgc_flush_zero(h);
     MgcLattice& L = h->L;
-    { const int rc = mgc_launch_readout(h, 1, nullptr); if (rc) return rc; }
-    MGC_HIP(h, hipMemcpyAsync(h->h_scalar, h->d_scalar, 8 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    { const int rc = mgc_launch_readout(h, MGC_S_CUT, nullptr); if (rc) return rc; }
+    MGC_HIP(h, hipMemcpyAsync(h->h_scalar, h->d_scalar, MGC_S_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (!h->op_spans.empty()) MGC_HIP(h, hipMemcpyAsync(h->h_count, L.count, MGC_NCOUNT * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     MGC_HIP(h, hipStreamSynchronize(h->stream));
     if (!h->op_spans.empty()) { /* the solve was driven launch by launch (mgc_solver_op): its kernel times */
@@ -5855,7 +5942,7 @@ int mgc_finish(mgc_handle h, double* flow_partial)
         h->stats.discharge_wave_tiles = L.ndir == 6 ? h->h_count[MGC_CNT_WAVE_TILES] : h->stats.discharge_tiles;
         h->op_spans.clear();
     }
-    h->flow = h->flow_const + h->h_scalar[1];
+    h->flow = h->flow_const + h->h_scalar[MGC_S_CUT];
     h->solved = true;
     h->converged = false; /* (driven launch by launch, or a slab: whether the schedule ended is the caller's knowledge) */
     h->labels_on_host = false;
@@ -5965,9 +6052,9 @@ int mgc_get_edge(mgc_handle h, int64_t i, int64_t j, double* out)
     mgc_node_to_tile(L, i, tile, loc);
     /* residual after maxflow() like Graph::get_edge (graph.h:482-498); before it the residuals ARE the built capacities */
     const double* src = L.rcap + ((int64_t)tile * L.ndir + d) * MGC_TV + loc;
-    MGC_HIP(h, hipMemcpyAsync(h->h_scalar + 6, src, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    MGC_HIP(h, hipMemcpyAsync(h->h_scalar + MGC_S_EDGE, src, sizeof(double), hipMemcpyDeviceToHost, h->stream));
     MGC_HIP(h, hipStreamSynchronize(h->stream));
-    *out = h->h_scalar[6];
+    *out = h->h_scalar[MGC_S_EDGE];
     return MGC_OK;
 }
 
@@ -6094,5 +6181,11 @@ int mgc_get_stats(mgc_handle h, mgc_stats* out)
 
 } /* extern "C" */
 
-/* (behind everything else of the file: the kernels of the solve keep their places in the code object) */
-#include "mgc_reach_driver.inl"
+/* The drivers that bring kernels of their own, behind everything else of the file and in this order: a kernel lies in the code
+ * object where the host code first names it, and the kernels of the solve keep their places ("Headline check") */
+#include "mgc_reach_driver.inl"      /* the cut sets */
+#include "mgc_binned_driver.inl"     /* the binned regional term */
+#include "mgc_label_hist_driver.inl" /* the histograms over every voxel */
+#include "mgc_cc_driver.inl"         /* the connected components */
+#include "mgc_edt_driver.inl"        /* the Euclidean distance transform and the surface metrics */
+#include "mgc_geo_driver.inl"        /* the geodesic distance transform and its regional term */

@@ -1,7 +1,7 @@
 /*
  * mgc_label_hist_driver.inl -- the host side of mgc_label_histograms: the histograms of the feature image over every
- * voxel, split by the labels of the current cut or by a label plane of the caller's.  Included ONCE, by the last line of
- * mgc_binned_driver.inl: the kernel of mgc_label_hist_ops.inl comes in here, behind every other kernel of the library, so that
+ * voxel, split by the labels of the current cut or by a label plane of the caller's.  Included ONCE, at the end of
+ * mgc_kernels.hip behind mgc_binned_driver.inl: the kernel of mgc_label_hist_ops.inl comes in here, behind those, so that
  * the kernels before it keep their places in the code object ("Headline check").  Every check comes before the first
  * write, and the call leaves the handle as it was: it reads the image and the labels, and what it allocates goes back to the pool
  * before it returns.
@@ -80,9 +80,7 @@ int mgc_label_histograms(mgc_handle h, const uint8_t* labels, int64_t nbins, dou
     if (host[words - 1] != MGC_BINNED_NONE) {
         const int64_t id = (int64_t)host[words - 1];
         double v = 0.0;
-        float vf = 0.f;
-        if (dtype == MGC_F32) { MGC_HIP(h, hipMemcpy(&vf, (const float*)image + id, sizeof(float), hipMemcpyDeviceToHost)); v = vf; }
-        else MGC_HIP(h, hipMemcpy(&v, (const double*)image + id, sizeof(double), hipMemcpyDeviceToHost));
+        MGC_HIP(h, mgc_fetch_value(image, dtype, id, &v));
         return mgc_fail(h, MGC_ERR_INVALID, "mgc_label_histograms: image[%lld] = %g: the feature image must be finite", (long long)id, v);
     }
     for (int64_t b = 0; b < nbins; ++b) { fg_hist[b] = (int64_t)host[(size_t)b]; bg_hist[b] = (int64_t)host[(size_t)(nbins + b)]; }
@@ -92,6 +90,3 @@ int mgc_label_histograms(mgc_handle h, const uint8_t* labels, int64_t nbins, dou
 }
 
 } /* extern "C" */
-
-/* (behind the kernel of this file as well: the connected components, DESIGN 16 -- the last code of the library) */
-#include "mgc_cc_driver.inl"

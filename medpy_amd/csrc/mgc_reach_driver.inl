@@ -1,36 +1,17 @@
 /*
  * mgc_reach_driver.inl -- the host side of mgc_cut_sets and mgc_cut_sets_tol (13b): both drivers, their entry points
- * and info getters, and what the two share.  Included ONCE, at the very end of mgc_kernels.hip: the kernels of mgc_reach_ops.inl
- * and mgc_reach_tol_ops.inl come in here, behind every other kernel of the file, so that the kernels of the solve keep their places
+ * and info getters, and what the two share.  Included ONCE, as the first of the drivers at the end of mgc_kernels.hip: the kernels of mgc_reach_ops.inl
+ * and mgc_reach_tol_ops.inl come in here, behind every other kernel of that file, so that the kernels of the solve keep their places
  * in the code object ("Headline check").
  *
  * Everything a call writes is its own: mark planes, stamps, C-order planes, count block (and, at a tolerance, the scale plane and
  * the thresholded mask plane) come from the pool and go back.  Of the handle a call uses the two relabel lists with their counters
  * (empty between two solves, cleared again on the way out; at a tolerance they carry both floods, one after the other), the counter
- * look of the schedule (read_counts), and the scratch of the cut value (d_part, d_part2, slots 4 and 5 of d_scalar).  Labels, label
+ * look of the schedule (read_counts), and the scratch of the cut value (d_part, d_part2, MGC_S_CUT_SOURCE and MGC_S_CUT_SINK of d_scalar).  Labels, label
  * summaries, snapshot and residual state are read only.
  */
 #include "mgc_reach_ops.inl"
 #include "mgc_reach_tol_ops.inl"
-
-/* the pool blocks of one call: get() after a failed get() allocates nothing, err is the first error */
-struct MgcReachBlocks {
-    std::vector<void*> held;
-    hipError_t err = hipSuccess;
-    void* get(size_t bytes)
-    {
-        void* p = nullptr;
-        if (err == hipSuccess) err = mgc_dmalloc(&p, bytes);
-        if (p) held.push_back(p);
-        return p;
-    }
-    void release()
-    {
-        for (void* p : held) (void)mgc_dfree(p);
-        held.clear();
-    }
-    ~MgcReachBlocks() { release(); }
-};
 
 /* One flood to its fixpoint: launch(cur, nxt, epoch) is one pass over list `cur` that fills list `nxt`.  Passes go out in stretches of
  * `batch` between two looks at the length of the list the next pass would consume; both lists are cleared on the way out. */
@@ -64,7 +45,7 @@ struct MgcReachCall {
     const MgcLayout lay;
     const char* const name; /* of the entry point: the roctx range and the head of an error message */
     MgcRange range;
-    MgcReachBlocks pool;
+    MgcBlocks pool;
     Dev dev;
     const bool timing;
     const size_t ntv, nvox8;
@@ -116,7 +97,7 @@ struct MgcReachCall {
     /* the scalars to the host, on a drained stream */
     hipError_t scalars(hipError_t e)
     {
-        if (e == hipSuccess) e = hipMemcpyAsync(h->h_scalar, h->d_scalar, 8 * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(h->h_scalar, h->d_scalar, MGC_S_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
         return e;
     }
@@ -136,9 +117,7 @@ struct MgcReachCall {
     int end(hipError_t e)
     {
         pool.release();
-        if (e == hipSuccess) return MGC_OK;
-        (void)hipGetLastError();
-        return mgc_fail(h, e == hipErrorOutOfMemory ? MGC_ERR_OOM : MGC_ERR_HIP, "%s: %s", name, hipGetErrorString(e));
+        return e == hipSuccess ? MGC_OK : mgc_hip_fail(h, name, e);
     }
 };
 
@@ -167,7 +146,7 @@ static int mgc_cut_sets_on(mgc_handle h, const MgcLayout lay, uint8_t* from_sour
         c.template flood<false>(L.ndir == 6 ? (const void*)L.rmask : (const void*)L.rmask32, marks, stamp, info + MGC_REACH_PASSES);
         hipLaunchKernelGGL(k_reach_readout, dim3(c.wgs), dim3(256), 0, h->stream, L, (const uint8_t*)marks, d_fs, d_amb, cnt3);
         hipLaunchKernelGGL(k_reach_sum, dim3(1), dim3(MGC_TV), 0, h->stream, (const int32_t*)cnt3, L.ntiles, info);
-        c.cut_value(d_fs, 4); /* (R_s | V \ R_s) */
+        c.cut_value(d_fs, MGC_S_CUT_SOURCE); /* (R_s | V \ R_s) */
         c.dev.check(hipGetLastError());
         e = c.dev.first_error;
     }
@@ -177,7 +156,7 @@ static int mgc_cut_sets_on(mgc_handle h, const MgcLayout lay, uint8_t* from_sour
     if (rc != MGC_OK) return rc;
     for (int k = 0; k < 8; ++k) h->cut_info[k] = (int64_t)h_info[k];
     h->cut_info[7] = 0;
-    h->cut_source = h->flow_const + h->h_scalar[4];
+    h->cut_source = h->flow_const + h->h_scalar[MGC_S_CUT_SOURCE];
     h->cut_info_valid = true;
     /* no error: the note says where the time of this call went (tools/gpu_cut_sets.py records it) */
     (void)mgc_fail(h, MGC_OK, "mgc_cut_sets: device_ms=%.3f download_ms=%.3f", c.ms(c.t0, c.t1), c.ms(c.t1, Clock::now()));
@@ -240,8 +219,8 @@ static int mgc_cut_sets_tol_on(mgc_handle h, const MgcLayout lay, double tol, ui
         t = Clock::now();
         hipLaunchKernelGGL(k_reach_readout_tol, dim3(c.wgs), dim3(256), 0, h->stream, L, (const uint8_t*)fwd, (const uint8_t*)bwd, d_fs, d_ts, d_amb, d_ns, cnt3);
         hipLaunchKernelGGL(k_reach_sum, dim3(1), dim3(MGC_TV), 0, h->stream, (const int32_t*)cnt3, L.ntiles, info);
-        c.cut_value(d_fs, 4); /* (R_s | V \ R_s) */
-        c.cut_value(d_ns, 5); /* (V \ R_t | R_t) */
+        c.cut_value(d_fs, MGC_S_CUT_SOURCE); /* (R_s | V \ R_s) */
+        c.cut_value(d_ns, MGC_S_CUT_SINK); /* (V \ R_t | R_t) */
         c.dev.check(hipGetLastError());
         e = c.scalars(c.dev.first_error);
         ms_phase[4] = c.ms(t, Clock::now());
@@ -254,8 +233,8 @@ static int mgc_cut_sets_tol_on(mgc_handle h, const MgcLayout lay, double tol, ui
     double scale_max = 0.0;
     memcpy(&scale_max, &h_info[MGC_REACHT_SCALE_MAX], sizeof(double));
     h->cut_tol_vals[0] = tol;
-    h->cut_tol_vals[1] = h->flow_const + h->h_scalar[4];
-    h->cut_tol_vals[2] = h->flow_const + h->h_scalar[5];
+    h->cut_tol_vals[1] = h->flow_const + h->h_scalar[MGC_S_CUT_SOURCE];
+    h->cut_tol_vals[2] = h->flow_const + h->h_scalar[MGC_S_CUT_SINK];
     h->cut_tol_vals[3] = scale_max;
     h->cut_tol_info_valid = true;
     /* no error: the note says where the time of this call went (tools/gpu_cut_sets_tol.py records it) */
@@ -315,6 +294,3 @@ int mgc_get_cut_sets_tol_info(mgc_handle h, int64_t* out16, double* out4)
 }
 
 } /* extern "C" */
-
-/* (behind the kernels of this file as well: the binned regional term, DESIGN 14 -- the last code of the library) */
-#include "mgc_binned_driver.inl"

@@ -253,11 +253,10 @@ def test_header_table_and_library_agree_on_the_new_calls():
     text = open(os.path.join(build.CSRC, "mgc_cc.h")).read()
     # the steps stay plain C++: a stand-alone program includes them
     assert "hip_runtime" not in text and "__global__" not in text and "__device__" not in text
-    # behind every other kernel of the library: the driver of the label histograms ends on the include of this one
-    lines = [ln for ln in open(os.path.join(build.CSRC, "mgc_label_hist_driver.inl")).read().splitlines() if ln.strip()]
-    assert lines[-1] == '#include "mgc_cc_driver.inl"'
-    for name in ("mgc_kernels.hip", "mgc_reach_driver.inl", "mgc_binned_driver.inl"):
-        assert '#include "mgc_cc' not in open(os.path.join(build.CSRC, name)).read(), name
+    # behind every kernel that was there before it: at the end of the kernel file behind the driver of the label histograms, and nothing
+    # in front includes it
+    import driver_chain
+    driver_chain.assert_behind_everything_before_it("mgc_cc_driver.inl", "mgc_cc")
 
 
 def test_classes_and_value_errors_without_a_library():

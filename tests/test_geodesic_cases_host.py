@@ -212,11 +212,9 @@ def test_header_table_and_library_agree_on_the_new_calls():
     assert int(re.search(r"#define MGC_GEO_SWEEP_CAP (\d+)", text).group(1)) == gc.SWEEP_CAP
     assert text.count("#pragma clang fp contract(off)") >= 2 and "-ffp-contract=off" in build.FLAGS
     assert "sqrt" not in open(os.path.join(build.CSRC, "mgc_geo_ops.inl")).read()   # the device takes no square root
-    # behind every other kernel of the library: the driver of the Euclidean transform ends on the include of this one
-    lines = [ln for ln in open(os.path.join(build.CSRC, "mgc_edt_driver.inl")).read().splitlines() if ln.strip()]
-    assert lines[-1] == '#include "mgc_geo_driver.inl"'
-    for name in ("mgc_kernels.hip", "mgc_reach_driver.inl", "mgc_binned_driver.inl", "mgc_label_hist_driver.inl", "mgc_cc_driver.inl"):
-        assert '#include "mgc_geo' not in open(os.path.join(build.CSRC, name)).read(), name
+    # behind every other kernel of the library: the last of the drivers at the end of the kernel file, and nothing in front includes it
+    import driver_chain
+    driver_chain.assert_behind_everything_before_it("mgc_geo_driver.inl", "mgc_geo")
 
 
 def test_classes_and_value_errors_without_a_library():

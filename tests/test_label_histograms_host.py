@@ -252,8 +252,7 @@ def test_header_table_and_library_agree_on_the_new_call():
     # the run merging stays plain C++: a stand-alone program includes it
     assert "hip_runtime" not in text and "__global__" not in text and "__device__" not in text
     assert int(re.search(r"#define MGC_LH_GROUP (\d+)", text).group(1)) == GROUP
-    # behind every other kernel of the library: the binned driver ends on the include of this one, and nothing else includes it
-    lines = [ln for ln in open(os.path.join(build.CSRC, "mgc_binned_driver.inl")).read().splitlines() if ln.strip()]
-    assert lines[-1] == '#include "mgc_label_hist_driver.inl"'
-    for name in ("mgc_kernels.hip", "mgc_reach_driver.inl", "mgc_binned_ops.inl"):
-        assert '#include "mgc_label_hist' not in open(os.path.join(build.CSRC, name)).read(), name
+    # behind every kernel that was there before it: at the end of the kernel file behind the binned driver, and nothing else includes it
+    import driver_chain
+    driver_chain.assert_behind_everything_before_it("mgc_label_hist_driver.inl", "mgc_label_hist")
+    assert '#include "mgc_label_hist' not in open(os.path.join(build.CSRC, "mgc_binned_ops.inl")).read()

@@ -265,11 +265,10 @@ def test_header_table_and_library_agree_on_the_new_calls():
     assert "hip_runtime" not in text and "__global__" not in text and "__device__" not in text   # plain C++: a stand-alone program includes it
     assert int(re.search(r"#define MGC_EDT_PANEL_LINE (\d+)", text).group(1)) == mc.LONG_LINE
     assert "-ffp-contract=off" in build.FLAGS
-    # behind every other kernel of the library: the driver of the components ends on the include of this one
-    lines = [ln for ln in open(os.path.join(build.CSRC, "mgc_cc_driver.inl")).read().splitlines() if ln.strip()]
-    assert lines[-1] == '#include "mgc_edt_driver.inl"'
-    for name in ("mgc_kernels.hip", "mgc_reach_driver.inl", "mgc_binned_driver.inl", "mgc_label_hist_driver.inl"):
-        assert '#include "mgc_edt' not in open(os.path.join(build.CSRC, name)).read(), name
+    # behind every kernel that was there before it: at the end of the kernel file behind the driver of the components, and nothing in
+    # front includes it
+    import driver_chain
+    driver_chain.assert_behind_everything_before_it("mgc_edt_driver.inl", "mgc_edt")
 
 
 def test_classes_and_value_errors_without_a_library():
