@@ -471,6 +471,29 @@ int mgc_geodesic_distance(mgc_handle h, const uint8_t* seeds, int source, int fu
 int mgc_add_tweights_geodesic(mgc_handle h, int full, double gamma, double step, const double* spacing, double lam);
 int mgc_update_tweights_geodesic(mgc_handle h, int full, double gamma, double step, const double* spacing, double lam);
 
+/* Anisotropic diffusion of an image (Perona-Malik, options 1 and 2; Tukey's biweight, option 3) on the device: MedPy's
+ * medpy.filter.smoothing.anisotropic_diffusion (the definition is medpy_amd/csrc/mgc_diffuse.h, stated there once).  The
+ * image is converted to float32, every operation of an iteration is an IEEE float32 operation rounded on its own, and one launch
+ * advances the whole volume by one iteration between two float32 buffers.  Options 2 and 3 equal the reference value for value;
+ * option 1 takes exp in f64 and rounds it once, which is close to NumPy's float32 exp and not equal.  kappa finite and > 0, gamma
+ * finite, spacing NULL (unity) or ndim finite positive values, niter >= 0 (0: the float32 copy).
+ *   mgc_diffuse_image: handle-free, like msg_region_sums: image is the caller's (host, C order, ndim 1..3, any dtype MGC_U8 ..
+ * MGC_F64), out nvox floats; the blocks come from the device's pool and are all given back.
+ *   mgc_diffuse: on a single handle; the image is the one mgc_marker_histograms reads (the feature image, else the boundary image),
+ * where it lies on the device.  keep = 0: nothing on the handle changes (labels, residual graph, statistics, launch counts,
+ * device_bytes stay; the pool gets every block back).  keep = 1: the result becomes the handle's feature image as MGC_F32, exactly
+ * as if mgc_set_feature_image had uploaded it (counted in device_bytes, replacing an earlier one): the histogram and geodesic
+ * terms then read the smoothed image without it crossing the bus; out may be NULL.
+ *   out4 (or NULL) = {iterations run, bricks per launch, 0, 0}.  After a call that went through, mgc_last_error (of the handle;
+ * of NULL for mgc_diffuse_image) holds a note of where its time went (upload_ms, iterate_ms, download_ms).
+ *   Refusals, before anything is written: MGC_ERR_INVALID for ndim outside 1..3, an extent < 1, a NULL image or shape, a bad dtype,
+ * niter < 0, option outside 1..3, kappa not finite or <= 0, gamma not finite, a spacing not finite and positive, keep other than
+ * 0 / 1, out NULL with keep = 0; MGC_ERR_STATE for a handle without any image; MGC_ERR_UNSUPPORTED on a slab handle; MGC_ERR_OOM
+ * before anything changed. */
+int mgc_diffuse_image(int device, int ndim, const int64_t* shape, const void* image, int dtype, int niter, double kappa, double gamma, const double* spacing, int option,
+                      float* out, int64_t* out4);
+int mgc_diffuse(mgc_handle h, int niter, double kappa, double gamma, const double* spacing, int option, int keep, float* out, int64_t* out4);
+
 /* Runs the n-link / t-link kernels: the residual graph is now resident in HBM. */
 int mgc_build(mgc_handle h);
 

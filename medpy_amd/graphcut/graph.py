@@ -404,6 +404,7 @@ class VoxelGraph(object):
         if _lib.device_count() < 1:
             raise _lib.MedpyHipError(_lib.ERR_NO_DEVICE, "no HIP device visible; medpy_amd has no CPU fallback")
         self._shape = tuple(int(s) for s in shape)
+        self._device = int(device)
         nd = len(self._shape)
         if nd < 1 or nd > 3:
             raise NotImplementedError("medpy_amd: %d-D lattices are not implemented (1-D..3-D are)" % nd)
@@ -1174,6 +1175,31 @@ class VoxelGraph(object):
         out8 = self._geo_info if self._geo_info is not None else numpy.zeros(8, dtype=numpy.int64)
         return dict(zip(self.GEODESIC_INFO_KEYS, out8.tolist()))
 
+    # -- anisotropic diffusion of the image the graph holds
+    _diffusion_info = None         # out4 of the last anisotropic_diffusion
+
+    def anisotropic_diffusion(self, niter, kappa, gamma, voxelspacing=None, option=1, keep=False, download=True):
+        """Anisotropic diffusion (``medpy_amd.filter.anisotropic_diffusion`` has the definition) of the image the graph holds -- its
+        feature image, else the image of its boundary term -- where it lies on the device (mgc_diffuse).  Returns the float32 array
+        of the volume's shape, or None with ``download=False`` (which needs ``keep=True``).  ``keep=True``: the result becomes
+        the graph's feature image, as ``set_feature_image`` of it would, without crossing the bus: ``marker_histograms()``,
+        ``label_histograms()``, the histogram and the geodesic terms read the smoothed image from then on.  ``keep=False``: nothing
+        on the graph changes.  ``diffusion_info()`` has the counts."""
+        from ..filter.smoothing import check_arguments
+        n, kappa, gamma, sp, option = check_arguments("anisotropic_diffusion", len(self._shape), niter, kappa, gamma, voxelspacing, option)
+        if not keep and not download:
+            raise ValueError("anisotropic_diffusion: download=False needs keep=True (the result would be lost)")
+        out = numpy.empty(self._shape, dtype=numpy.float32) if download else None
+        out4 = numpy.zeros(4, dtype=numpy.int64)
+        self._call("mgc_diffuse", n, kappa, gamma, None if sp is None else _lib.ptr(sp), option, int(bool(keep)), None if out is None else _lib.ptr(out), _lib.ptr(out4))
+        self._diffusion_info = out4
+        return out
+
+    def diffusion_info(self):
+        """of the last ``anisotropic_diffusion``: ``iterations`` run and ``bricks`` per launch"""
+        out4 = self._diffusion_info if self._diffusion_info is not None else numpy.zeros(4, dtype=numpy.int64)
+        return {"iterations": int(out4[0]), "bricks": int(out4[1])}
+
     def _geo_term_args(self, what, gamma, lam, step, spacing, connectivity):
         return (self._geo_number(what, "gamma", gamma), self._geo_number(what, "lam", lam), self._geo_number(what, "step", step),
                 self._edt_spacing(what, spacing), self._geo_full(what, connectivity))
@@ -1494,6 +1520,14 @@ class SparseGraph(object):
     def refit_regional_geodesic(self, gamma=None, lam=None):
         """The geodesic regional term exists for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
         self._no_metrics("refit_regional_geodesic")
+
+    def anisotropic_diffusion(self, niter=1, kappa=50, gamma=0.1, voxelspacing=None, option=1, keep=False, download=True):
+        """The diffusion of the graph's image exists for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
+        self._no_metrics("anisotropic_diffusion")
+
+    def diffusion_info(self):
+        """The diffusion of the graph's image exists for the voxel lattices of 1-D..3-D volumes (VoxelGraph) only."""
+        self._no_metrics("diffusion_info")
 
     # -- the other minimum cuts (DESIGN 13c)
     CUT_SETS_INFO_KEYS = ("from_source", "to_sink", "ambiguous", "forward_passes", "forward_seeds", "backward_passes", "backward_seeds",
@@ -2243,6 +2277,13 @@ class EmbeddedLatticeGraph(object):
     def refit_regional_geodesic(self, gamma=None, lam=None):
         """of the lattice part (``VoxelGraph.refit_regional_geodesic``: ValueError, such a graph is built without the term)"""
         return self._inner.refit_regional_geodesic(gamma, lam)
+
+    def anisotropic_diffusion(self, niter, kappa, gamma, voxelspacing=None, option=1, keep=False, download=True):
+        """of the lattice part (``VoxelGraph.anisotropic_diffusion``), in the lattice's shape"""
+        return self._inner.anisotropic_diffusion(niter, kappa, gamma, voxelspacing, option, keep, download)
+
+    def diffusion_info(self):
+        return self._inner.diffusion_info()
 
     def stats(self):
         return self._inner.stats()
