@@ -494,6 +494,29 @@ int mgc_diffuse_image(int device, int ndim, const int64_t* shape, const void* im
                       float* out, int64_t* out4);
 int mgc_diffuse(mgc_handle h, int niter, double kappa, double gamma, const double* spacing, int option, int keep, float* out, int64_t* out4);
 
+/* The seeded watershed of an image on the device, and the minima its markers are made from: the two steps of MedPy's
+ * medpy_watershed.py between an image and the region image that graph_from_labels takes (the definition is
+ * medpy_amd/csrc/mgc_ws.h, stated there once).  Both are handle-free, like mgc_diffuse_image: image is the caller's (host, C order,
+ * ndim 1..3, dtype MGC_U8 .. MGC_I32 or MGC_F32), the work runs on a stream of its own, every block comes from the device's pool and
+ * all are given back.  Only image values are compared, nothing is rounded: the results are a definition, not an approximation.
+ *   mgc_watershed_image: markers nvox int32 (0: none, > 0: a label), mask nvox bytes (0: outside) or NULL, labels_out nvox int32.
+ * Face neighbourhood.  Every voxel gets the arrival key (H, D) -- H the level at which water from a marker reaches it (the lowest
+ * highest value of a path), D the steps since the path last rose -- as the least fixpoint of a relaxation over tiles, takes the
+ * neighbour with the smallest (key, index) below its own as parent, and the marker at the root of its chain as label; 0 outside
+ * the mask and where no marker connects.  A marker outside the mask is no marker.  On images without ties this is Meyer's
+ * priority flood; on plateaus the regions meet where the step counts meet.
+ *   out8 (or NULL) = {seed voxels, rounds (launches of the tile kernel), tile visits, sweeps, visits that ended at the sweep cap,
+ * reached voxels (the seeds among them), pointer-jumping rounds, 0}.
+ *   mgc_local_minima_image: mask_out[p] = (image[p] == scipy.ndimage.minimum_filter(image, size=size)[p]) (border `reflect`, the
+ * window placed as SciPy places it for even and odd sizes), nvox bytes; out4 (or NULL) = {minima, 0, 0, 0}.
+ *   After a call that went through, mgc_last_error(NULL) holds a note of where its time went (upload_ms, flood_ms, parent_ms,
+ * resolve_ms, download_ms; upload_ms, filter_ms, download_ms).
+ *   Refusals, before the first allocation: MGC_ERR_INVALID for ndim outside 1..3, an extent < 1, a NULL image, shape, markers or
+ * result, a bad dtype, a negative marker, size < 1, a float value that is not finite; MGC_ERR_UNSUPPORTED for the 64-bit dtypes
+ * (rank the values on the host and send MGC_U32) and for volumes of 2^32 - 1 voxels or more; MGC_ERR_OOM before anything changed. */
+int mgc_watershed_image(int device, int ndim, const int64_t* shape, const void* image, int dtype, const int32_t* markers, const uint8_t* mask, int32_t* labels_out, int64_t* out8);
+int mgc_local_minima_image(int device, int ndim, const int64_t* shape, const void* image, int dtype, int size, uint8_t* mask_out, int64_t* out4);
+
 /* Runs the n-link / t-link kernels: the residual graph is now resident in HBM. */
 int mgc_build(mgc_handle h);
 

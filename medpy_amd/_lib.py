@@ -173,6 +173,8 @@ SIGNATURES = {
     "mgc_update_tweights_geodesic": (_INT, [_VP, _INT, _DBL, _DBL, _VP, _DBL]),
     "mgc_diffuse_image": (_INT, [_INT, _INT, C.POINTER(_I64), _VP, _INT, _INT, _DBL, _DBL, _VP, _INT, _VP, _VP]),
     "mgc_diffuse": (_INT, [_VP, _INT, _DBL, _DBL, _VP, _INT, _INT, _VP, _VP]),
+    "mgc_watershed_image": (_INT, [_INT, _INT, C.POINTER(_I64), _VP, _INT, _VP, _VP, _VP, _VP]),
+    "mgc_local_minima_image": (_INT, [_INT, _INT, C.POINTER(_I64), _VP, _INT, _INT, _VP, _VP]),
     "mgc_build": (_INT, [_VP]),
     "mgc_get_nweights": (_INT, [_VP, _INT, _VP]),
     "mgc_get_tweights": (_INT, [_VP, _VP]),

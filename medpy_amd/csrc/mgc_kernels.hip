@@ -6184,6 +6184,7 @@ int mgc_get_stats(mgc_handle h, mgc_stats* out)
 /* The drivers that bring kernels of their own, behind everything else of the file and in this order: a kernel lies in the code
  * object where the host code first names it, and the kernels of the solve keep their places ("Headline check") */
 #include "mgc_diffuse_driver.inl"   /* anisotropic diffusion of the image: in front of the six, whose block ends the file */
+#include "mgc_ws_driver.inl"        /* the seeded watershed and the minima of its markers: behind the diffusion, in front of the six */
 #include "mgc_reach_driver.inl"      /* the cut sets */
 #include "mgc_binned_driver.inl"     /* the binned regional term */
 #include "mgc_label_hist_driver.inl" /* the histograms over every voxel */
